@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the hot path: fingerprint generation, 1-s segments per second.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of  audio -> log-mel -> encoder -> L2-normalised fingerprint
 over one batch of 640 synthetic 1-s segments that are already resident in HBM
@@ -15,12 +15,24 @@ rank 0's JSON line and exits with the child's return code; under torch.distribut
 (WORLD_SIZE set) it is one of the ranks.
 
 The timed region (EXACTLY --steps steps between barrier + synchronize) is repeated
---repeats times; `ms_per_step` / `value` are the MEDIAN region, `spread` holds all of them.
+--repeats times (default 1; 5 with --full); `ms_per_step` / `value` are the MEDIAN region,
+`spread` holds all of them.
+
+--dump-outputs DIR: after the timed steps, the fingerprints of the last timed step (what a
+caller of the generate path receives: float32 (640, 128), rank 0's batch) are written to
+DIR/embedding.npy.  Inputs (seeded audio) and weights (seed 0) are the same in every run.
+
+A plain run sets up, warms up, times the steps and prints the line with `roofline` (taken
+from the timed region itself).  Everything that needs runs of its own is measured only with
+--full: the per-stage split (`stage_ms_per_step`, `frontend_hbm`), and the objects below.
 
 Prints ONE JSON line (rank 0).  Extra objects:
   roofline     the dominant kernel (the fp32-MFMA implicit-GEMM convs): algorithmic
                FLOPs per launch / mean launch duration from HIP events recorded on the
                launch stream inside the timed region, vs the 157.3 TFLOP/s fp32 matrix peak
+With --full:
+  pipelined, bf16x3_experimental, bf16x6_f32_equivalent_experimental
+               the same steps on 4 streams, and the two split-bf16 arithmetics
   cpu_baseline the oracle's torch-CPU restatement of the same graph timed on ALL host
                cores of this box on a bounded sample (kind "port": TensorFlow is absent)
   e2e_generate disk -> .mm through `write_fingerprints` on the 100-clip config-1 set and a
@@ -47,6 +59,7 @@ if ROOT not in sys.path:
 BSZ = 640                      # BASELINE.json configs[1]
 FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense
 BF16_MFMA_PEAK_TFLOPS = 2500.0  # MI355X_MICROARCH.md: v_mfma_f32_32x32x16_bf16, dense (never the 2:1-sparsity figure)
+PROFILE_MAX_FORWARDS = 4096    # the most forwards nafp_encoder_profile_enable stamps (csrc/api.hip); later ones run unstamped
 
 
 def conv_effective_macs(input_shape=(256, 32, 1)):
@@ -453,9 +466,15 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--streams', type=int, default=1,
                     help='streams of the timed region (1: every kernel runs alone, so HIP-event launch '
-                         'durations are the kernels own).  With 1, a second region with 4 streams is '
+                         'durations are the kernels own).  With 1 and --full, a second region with 4 streams is '
                          'timed afterwards and reported as "pipelined".')
-    ap.add_argument('--repeats', type=int, default=5, help='timed regions of --steps steps each; the median is reported')
+    ap.add_argument('--repeats', type=int, default=None,
+                    help='timed regions of --steps steps each; the median is reported (default 1; 5 with --full)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beyond the headline: per-stage split, 4 streams, split-bf16 arithmetics, '
+                         'train regions, disk -> .mm, full-scale generate, CPU baseline (the --no-* options below apply here)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the fingerprints of the last timed step to DIR/embedding.npy (float32)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-e2e', action='store_true', help='skip the disk -> .mm figures (reported as "e2e_generate")')
     ap.add_argument('--no-train', action='store_true', help='skip the contrastive-train region (reported as "train")')
@@ -468,6 +487,10 @@ def main():
                     help='skip the extra 4-stream region (used under rocprofv3 so that its per-kernel '
                          'averages cover the single-stream launches only)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(spawn_ranks(args.gpus))                # nothing above has touched the GPU
@@ -543,7 +566,7 @@ def main():
     # set-up each), so everything else -- the per-conv split, conv0, the front end, the tail -- is taken from a second,
     # untimed pass below.
     reps = max(1, args.repeats)
-    m_fp.profile_enable(args.steps * reps, coarse=2)
+    m_fp.profile_enable(min(args.steps * reps, PROFILE_MAX_FORWARDS), coarse=2)     # roofline = mean over the stamped steps
     ev = None
     regions = []
     for _ in range(reps):
@@ -564,21 +587,26 @@ def main():
         regions.append(el)
     el = sorted(regions)[len(regions) // 2]             # the median region is the one reported
     assert emb.shape == (BSZ, 128) and bool(torch.isfinite(emb).all())
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'embedding.npy'), emb.float().cpu().numpy())
 
     prof = m_fp.profile_read()
-    # per-stage split: the same steps once more on one stream with a stamp after every launch (outside the timed region)
-    n_fine = min(args.steps, 8)
-    m_fp.profile_enable(n_fine)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2 * n_fine)]
-    for i in range(n_fine):
-        with torch.cuda.stream(streams[0]):
-            ev[2 * i].record()
-            feat = m_pre(pool[i % n_pool], group_size=BSZ, defer=True)
-            ev[2 * i + 1].record()
-            m_fp(feat)
-    torch.cuda.synchronize()
-    prof_fine = m_fp.profile_read()
-    mel_ms = sum(ev[2 * i].elapsed_time(ev[2 * i + 1]) for i in range(n_fine)) / n_fine
+    if args.full:
+        # per-stage split: the same steps once more on one stream with a stamp after every launch (outside the timed region)
+        n_fine = min(args.steps, 8)
+        m_fp.profile_enable(n_fine)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2 * n_fine)]
+        for i in range(n_fine):
+            with torch.cuda.stream(streams[0]):
+                ev[2 * i].record()
+                feat = m_pre(pool[i % n_pool], group_size=BSZ, defer=True)
+                ev[2 * i + 1].record()
+                m_fp(feat)
+        torch.cuda.synchronize()
+        prof_fine = m_fp.profile_read()
+        mel_ms = sum(ev[2 * i].elapsed_time(ev[2 * i + 1]) for i in range(n_fine)) / n_fine
     # Outside the timed region: the same steps on ONE stream, so that each kernel's duration is
     # its own (in the pipelined region kernels of different batches share the chip and the
     # per-launch durations include that sharing).
@@ -586,7 +614,7 @@ def main():
     # occupancy late convs of one batch overlap the large convs of the next.  Reported
     # separately; `value` stays the single-stream figure that `roofline` is consistent with.
     pipelined = None
-    if n_str == 1 and not args.no_pipelined:
+    if args.full and n_str == 1 and not args.no_pipelined:
         m_fp.profile_enable(0)
         ps = [torch.cuda.Stream(device=dev) for _ in range(4)]
 
@@ -615,7 +643,7 @@ def main():
     # split into hi + lo bf16 in registers, hi*hi + hi*lo + lo*hi on the bf16 matrix pipe, f32 accumulation:
     # NAFP_OPT_BF16X3).  Narrower arithmetic than the reference's f32, so its error against the f32 path is measured here.
     bf16x3, bf16x6 = None, None
-    if n_str == 1 and not args.no_pipelined:
+    if args.full and n_str == 1 and not args.no_pipelined:
         with torch.cuda.stream(streams[0]):
             ref_emb = m_fp(m_pre(pool[0], group_size=BSZ, defer=True)).clone()
             m_fp.set_option(3, 1)
@@ -644,7 +672,7 @@ def main():
         bel6 = time.perf_counter() - tb0
         # its own roofline: the span of the GEMM convs from the library's dispatch-attached stamps (one span per step, as for `roofline`),
         # and a per-conv pass for the table of profiles/r06_summary.md
-        m_fp.profile_enable(args.steps, coarse=2)
+        m_fp.profile_enable(min(args.steps, PROFILE_MAX_FORWARDS), coarse=2)
         with torch.cuda.stream(streams[0]):
             for i in range(args.steps):
                 m_fp(m_pre(pool[i % n_pool], group_size=BSZ, defer=True))
@@ -709,7 +737,7 @@ def main():
                   'note': 'experimental option NAFP_OPT_BF16X3 on the unsplit GEMM convs (convs 1-6, 8 at BSZ 640); NOT the '
                           "reference's arithmetic, not part of `value`"}
     train, train_1280, train_r640, train_x6 = None, None, None, None
-    if not args.no_train:
+    if args.full and not args.no_train:
         train = train_region(cfg, world, rank, dist, args.train_bsz, args.train_steps, torch, repeats=args.train_repeats)
         if world == 1:
             # EXPERIMENTAL, a separate object, never `train`: the same step with the GEMM products of forward_train and of the transposed
@@ -738,7 +766,7 @@ def main():
             except Exception as ex:                      # noqa: BLE001
                 train_r640 = {'error': f'{type(ex).__name__}: {ex}'[:400]}
     e2e, fullscale = None, None
-    if world == 1 and not args.no_e2e:
+    if args.full and world == 1 and not args.no_e2e:
         try:                                            # (secondary objects: a full disk must not cost the headline line)
             e2e = e2e_generate(cfg, torch)
         except OSError as ex:
@@ -749,7 +777,7 @@ def main():
             except OSError as ex:
                 fullscale = {'error': f'{type(ex).__name__}: {ex}'[:400]}
     iso = None
-    if n_str > 1:
+    if args.full and n_str > 1:
         m_fp.profile_enable(6)
         for i in range(6):
             with torch.cuda.stream(streams[0]):
@@ -761,8 +789,6 @@ def main():
         gemm_flops_per_step = 2.0 * sum(macs[1:]) * BSZ            # the 15 implicit-GEMM launches
         gemm_ms = sum(sum(p[1:16]) for p in prof) / len(prof)      # per step, all 15 launches
         ach = gemm_flops_per_step / (gemm_ms * 1e-3) / 1e12
-        conv0_ms = sum(p[0] for p in prof_fine) / len(prof_fine)
-        tail_ms = sum(p[16] for p in prof_fine) / len(prof_fine)
         value = world * BSZ * args.steps / el
         traffic, traffic_src, fe_traffic, fe_kernel_us = None, None, None, None
         tp = os.path.join(ROOT, 'profiles', 'traffic.json')
@@ -794,34 +820,37 @@ def main():
                 'achieved': round(ach, 2), 'peak': FP32_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
                 'frac': round(ach / FP32_MFMA_PEAK_TFLOPS, 4), 'traffic': traffic, 'traffic_unit': 'bytes/launch',
                 'traffic_source': traffic_src,
-                'flops_per_launch_avg': gemm_flops_per_step / 15, 'ms_per_launch_avg': round(gemm_ms / 15, 5),
+                'flops_per_launch_avg': gemm_flops_per_step / 15, 'ms_per_launch_avg': round(gemm_ms / 15, 5), 'stamped_steps': len(prof),
                 'note': 'HIP events recorded by the library on the launch stream inside the timed region: one span per step '
                         'from the first GEMM-conv launch to the end of the last (split-K finish kernels and inter-launch gaps '
                         'included), average launch = span / 15' + ('' if n_str == 1 else f'; {n_str} batches are in flight on separate '
-                        'streams there, so launches of different batches share the chip; "isolated" = the same '
+                        'streams there, so launches of different batches share the chip') + ('' if not iso else '; "isolated" = the same '
                         'launches alone on one stream (un-timed pass after the region)')},
-            'stage_ms_per_step': {'melspec(2 kernels)': round(mel_ms, 4), 'conv0': round(conv0_ms, 4),
-                                  'conv_gemm x15': round(gemm_ms, 4), 'tail': round(tail_ms, 4),
-                                  'per_conv': [round(sum(p[k] for p in prof_fine) / len(prof_fine), 4) for k in range(17)],
-                                  'per_conv_note': '"conv_gemm x15" is the span timed inside the timed region; melspec, conv0, tail and '
-                                                   'per_conv (conv0, the 15 GEMM convs, tail) come from a second, untimed pass: each GEMM '
-                                                   'conv from the start of its first kernel to the end of its last (dispatch-attached time '
-                                                   'stamps, split-K finish kernel included), conv0 / tail / melspec between recorded '
-                                                   'events.  Stamping every launch still costs: these figures sum to ~10 % more than the '
-                                                   'timed span; un-stamped kernel durations are in profiles/*_summary.md'},
-            'frontend_hbm': {'bound': 'hbm', 'kernel': 'melspec_r16_kernel (STFT + mel + log; the max subtraction is applied by conv0 on load)',
-                             'algorithmic_bytes_per_segment': 32000 + 32768,
-                             'achieved': round(BSZ * (32000 + 32768) / (mel_ms * 1e-3) / 1e9, 2), 'peak': 8000.0, 'unit': 'GB/s',
-                             'frac': round(BSZ * (32000 + 32768) / (mel_ms * 1e-3) / 1e9 / 8000.0, 4),
-                             'kernel_us_rocprof': fe_kernel_us,
-                             'frac_at_kernel_time': round(BSZ * (32000 + 32768) / (fe_kernel_us * 1e-6) / 1e9 / 8000.0, 4) if fe_kernel_us else None,
-                             'note': '`achieved` divides by the time between two events around the whole stage (melspec_init_stats + the '
-                                     'kernel + launch gaps, measured in this run); kernel_us_rocprof is the kernel alone under rocprofv3 '
-                                     '(profiles/traffic.json)',
-                             'traffic': fe_traffic, 'traffic_unit': 'bytes/launch (640 segments)',
-                             'traffic_ratio_to_algorithmic': round(fe_traffic / (BSZ * (32000 + 32768)), 3) if fe_traffic else None},
         }
         out['config']['streams'] = n_str
+        if args.full:
+            conv0_ms = sum(p[0] for p in prof_fine) / len(prof_fine)
+            tail_ms = sum(p[16] for p in prof_fine) / len(prof_fine)
+            out['stage_ms_per_step'] = {'melspec(2 kernels)': round(mel_ms, 4), 'conv0': round(conv0_ms, 4),
+                                        'conv_gemm x15': round(gemm_ms, 4), 'tail': round(tail_ms, 4),
+                                        'per_conv': [round(sum(p[k] for p in prof_fine) / len(prof_fine), 4) for k in range(17)],
+                                        'per_conv_note': '"conv_gemm x15" is the span timed inside the timed region; melspec, conv0, tail and '
+                                                         'per_conv (conv0, the 15 GEMM convs, tail) come from a second, untimed pass: each GEMM '
+                                                         'conv from the start of its first kernel to the end of its last (dispatch-attached time '
+                                                         'stamps, split-K finish kernel included), conv0 / tail / melspec between recorded '
+                                                         'events.  Stamping every launch still costs: these figures sum to ~10 % more than the '
+                                                         'timed span; un-stamped kernel durations are in profiles/*_summary.md'}
+            out['frontend_hbm'] = {'bound': 'hbm', 'kernel': 'melspec_r16_kernel (STFT + mel + log; the max subtraction is applied by conv0 on load)',
+                                   'algorithmic_bytes_per_segment': 32000 + 32768,
+                                   'achieved': round(BSZ * (32000 + 32768) / (mel_ms * 1e-3) / 1e9, 2), 'peak': 8000.0, 'unit': 'GB/s',
+                                   'frac': round(BSZ * (32000 + 32768) / (mel_ms * 1e-3) / 1e9 / 8000.0, 4),
+                                   'kernel_us_rocprof': fe_kernel_us,
+                                   'frac_at_kernel_time': round(BSZ * (32000 + 32768) / (fe_kernel_us * 1e-6) / 1e9 / 8000.0, 4) if fe_kernel_us else None,
+                                   'note': '`achieved` divides by the time between two events around the whole stage (melspec_init_stats + the '
+                                           'kernel + launch gaps, measured in this run); kernel_us_rocprof is the kernel alone under rocprofv3 '
+                                           '(profiles/traffic.json)',
+                                   'traffic': fe_traffic, 'traffic_unit': 'bytes/launch (640 segments)',
+                                   'traffic_ratio_to_algorithmic': round(fe_traffic / (BSZ * (32000 + 32768)), 3) if fe_traffic else None}
         if pipelined:
             out['pipelined'] = pipelined
         if bf16x3:
@@ -847,7 +876,7 @@ def main():
                 'achieved': round(iso_ach, 2), 'frac': round(iso_ach / FP32_MFMA_PEAK_TFLOPS, 4),
                 'ms_per_launch_avg': round(iso_ms / 15, 5),
                 'per_conv_ms': [round(sum(p[k] for p in iso) / len(iso), 4) for k in range(17)]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline()
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + '\n').encode())

@@ -1,11 +1,13 @@
 """GPU: bench.py prints ONE JSON line that carries every field of the driver's contract (metric / value / unit /
 n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config,
-`roofline` and `cpu_baseline`), consistent with itself."""
+`roofline`, and with --full `cpu_baseline` and the secondary objects), consistent with itself.  A plain run times
+exactly --steps steps, measures nothing else, and --dump-outputs writes the fingerprints of its last step."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -13,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_line_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '2',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '2', '--full',
                         '--repeats', '3', '--train-steps', '2', '--train-bsz', '256'], cwd=ROOT, capture_output=True, text=True,
                        timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -86,7 +88,7 @@ def test_bench_two_ranks_on_one_gpu_prints_train_with_collective_timings(form):
     port = 29800 + (os.getpid() % 100)
     launcher = [] if form == 'bare' else ['-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
                                           '--master-addr', '127.0.0.1', '--master-port', str(port)]
-    r = subprocess.run([sys.executable] + launcher + [os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
+    r = subprocess.run([sys.executable] + launcher + [os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--full',
                                                       '--repeats', '2', '--train-steps', '2', '--train-bsz', '128'],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
@@ -104,3 +106,53 @@ def test_bench_two_ranks_on_one_gpu_prints_train_with_collective_timings(form):
     assert abs(sum(c['grad_piece_MB']) - 67.76) < 0.1
     # what the collectives leave exposed: the step minus rank 0's compute-only step of the same run
     assert abs(tr['exposed_comm_ms'] - (tr['ms_per_step'] - tr['no_process_group_ms_per_step'])) < 2e-3
+
+
+def test_plain_run_times_only_the_steps_and_dumps_the_last_one(nafp, cfg, tmp_path):
+    """`bench.py --steps K --warmup W` without --full: one timed region of exactly K steps, the headline fields and the
+    roofline of that region, none of the --full objects; --dump-outputs DIR holds the fingerprints of the last timed step,
+    equal to the same step recomputed in this process (same seeded audio, same seeded weights)."""
+    import torch
+    import bench
+    steps = 3
+    out_dir = tmp_path / 'dump'
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', '2',
+                        '--dump-outputs', str(out_dir)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'n_gpus', 'steps', 'warmup', 'roofline'):
+        assert k in d, k
+    assert d['steps'] == steps and d['warmup'] == 2 and d['repeats'] == 1 and len(d['spread']['ms_per_step_all']) == 1
+    assert d['unit'] == 'segments/s' and d['dtype'] == 'f32' and d['higher_is_better'] is True
+    assert abs(d['value'] - 640 / (d['ms_per_step'] / 1e3)) < 1e-3 * d['value']
+    for k in ('cpu_baseline', 'train', 'train_1280', 'train_rank640', 'train_x6_experimental', 'pipelined', 'bf16x3_experimental',
+              'bf16x6_f32_equivalent_experimental', 'e2e_generate', 'fullscale_generate', 'stage_ms_per_step', 'frontend_hbm'):
+        assert k not in d, k
+    assert sorted(os.listdir(out_dir)) == ['embedding.npy']
+    got = np.load(out_dir / 'embedding.npy')
+    assert got.dtype == np.float32 and got.shape == (640, 128) and np.isfinite(got).all()
+    m_pre = nafp.get_melspec_layer(cfg)
+    m_fp = nafp.FingerPrinter(emb_sz=cfg['MODEL']['EMB_SZ'], norm=cfg['MODEL']['BN'], seed=0, device=torch.device('cuda', 0))
+    x = bench.make_audio(640, (steps - 1) % 4, torch).cuda()            # the pool batch of the last timed step (rank 0)
+    want = m_fp(m_pre(x, group_size=640, defer=True)).cpu().numpy()
+    assert np.abs(got - want).max() < 1e-6
+
+
+def test_full_run_with_more_steps_than_the_library_stamps():
+    """The library stamps at most 4096 forwards (nafp_encoder_profile_enable): with more timed steps than that, --full
+    still runs every region; the rooflines average the stamped steps and the later ones run unstamped."""
+    steps = 4100
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', '1', '--full',
+                        '--repeats', '1', '--no-train', '--no-e2e', '--no-cpu-baseline', '--fullscale-rows', '0'],
+                       cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d['steps'] == steps and d['repeats'] == 1
+    assert d['roofline']['stamped_steps'] == 4096 and 0.2 < d['roofline']['frac'] < 1.0
+    x6 = d['bf16x6_f32_equivalent_experimental']
+    assert 0.05 < x6['roofline']['frac'] < 1.0 and x6['pipelined']['bit_identical_to_single_stream'] is True
+    assert d['pipelined']['value'] > 0 and 'stage_ms_per_step' in d

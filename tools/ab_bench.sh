@@ -6,7 +6,7 @@ ROUNDS=2
 if [ "$1" = "-r" ]; then ROUNDS=$2; shift 2; fi
 for r in $(seq 1 $ROUNDS); do
   for v in "$@"; do
-    env $v python bench.py --steps 15 --warmup 4 --repeats 3 --no-cpu-baseline --no-pipelined --no-train --no-e2e 2>/dev/null | tail -1 | \
+    env $v python bench.py --full --steps 15 --warmup 4 --repeats 3 --no-cpu-baseline --no-pipelined --no-train --no-e2e 2>/dev/null | tail -1 | \
       python -c "import json,sys; d=json.loads(sys.stdin.read()); pc=d['stage_ms_per_step']['per_conv']; print('%-28s' % '$v', d['value'], d['stage_ms_per_step']['conv_gemm x15'], round(pc[0],3), [round(x,3) for x in pc[1:6]], [round(x,3) for x in pc[6:10]], [round(x,3) for x in pc[10:16]], 'mel', d['stage_ms_per_step']['melspec(2 kernels)'])"
   done
 done

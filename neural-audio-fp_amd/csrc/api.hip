@@ -67,8 +67,10 @@ __global__ __launch_bounds__(256) void multi_copy_kernel(const CopyTable t) {
     if (bad && t.nonfinite) atomicOr(t.nonfinite, 1);
 }
 #define NAFP_OPT_DEBUG_SIDE_DELAY 6
-// TEST HOOK (NAFP_OPT_DEBUG_SIDE_DELAY): holds a stream for `us` microseconds (100 MHz real-time counter), so that a test can make the
-// weight-gradient stream lag the main stream deterministically and see whether every event is ordered behind what it stands for
+#define NAFP_OPT_DEBUG_SW_DELAY 7
+// TEST HOOKS (NAFP_OPT_DEBUG_SIDE_DELAY, NAFP_OPT_DEBUG_SW_DELAY): holds a stream for `us` microseconds (100 MHz real-time counter), so
+// that a test can make the weight-gradient stream lag the main stream -- or set_weights lag behind each of its early events --
+// deterministically and see whether every event is ordered behind what it stands for
 __global__ void debug_delay_kernel(long long us) {
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
     while ((long long)(__builtin_amdgcn_s_memrealtime() - t0) < us * 100) __builtin_amdgcn_s_sleep(32);
@@ -125,7 +127,7 @@ struct nafp_encoder {
     // so the ~0.3 ms chain of small G / Hb launches runs under conv0 and conv1 instead of in front of them (B = 640: the main
     // stream sat idle for 0.19 ms per step waiting for it; next to conv0, which saturates the HBM write path, the chain stretches
     // to 0.4 ms, hence the third event).  Same stream: no wait is enqueued.
-    hipEvent_t sw_copied = nullptr, sw_l1 = nullptr, sw_done = nullptr;      // (sw_l1: conv1's packed kernel and G / Hb are done too)
+    hipEvent_t sw_copied = nullptr, sw_l1 = nullptr, sw_done = nullptr;      // (sw_l1: conv1's packed kernel, G / Hb and -- NAFP_OPT_BF16X3 = 2 -- its bf16 terms are done too)
     hipStream_t sw_stream = nullptr;
     bool sw_recorded = false;
     // NAFP_OPT_FUSE_CONV0 (default: NAFP_FUSE0 env, else off).  Re-measured in round 4 on the current kernels (B = 640, same
@@ -192,6 +194,7 @@ struct nafp_encoder {
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_main[16] = {}, ev_side[16] = {};
     int debug_side_delay_us = 0;          // NAFP_OPT_DEBUG_SIDE_DELAY (tests only): the weight-gradient stream idles this long in front of its first launch of a pass
+    int debug_sw_delay_us = 0;            // NAFP_OPT_DEBUG_SW_DELAY (tests only): set_weights' stream idles this long right behind `sw_copied` and behind `sw_l1`
     // set_weights: the 15 G / Hb images are small, latency-bound launches (2 "samples"; the late ones stream 6-12 MB of
     // weights through a handful of workgroups): they run NAFP_SW_STREAMS abreast on helper streams of the handle, each
     // with its own split-K slab, between a fork and a join on the caller's stream.
@@ -373,17 +376,21 @@ extern "C" int nafp_encoder_destroy(nafp_encoder* e) {
     return NAFP_OK;
 }
 
-// NAFP_OPT_BF16X3 = 2: the three bf16 terms of every packed conv kernel and of its flipped form (conv.hip split_weights_multi_kernel)
-static int split_all_weights(nafp_encoder* e, hipStream_t st) {
+// NAFP_OPT_BF16X3 = 2: the three bf16 terms of the packed conv kernels j_lo..j_hi and of their flipped forms (conv.hip
+// split_weights_multi_kernel)
+static int split_weights(nafp_encoder* e, hipStream_t st, int j_lo, int j_hi) {
     SplitTable t; t.count = 0;
-    for (int j = 1; j < 16; ++j) {
+    for (int j = j_lo; j <= j_hi; ++j) {
         const int64_t n = (int64_t)e->geom[j].Cout * 3 * e->geom[j].Cin;
         t.wp[t.count] = e->d_w[j]; t.hm[t.count] = e->d_whm[j]; t.wl[t.count] = e->d_wl[j]; t.n8[t.count] = n / 8; t.K[t.count] = 3 * e->geom[j].Cin; ++t.count;
         if (e->geom[j].Cout % 16 == 0 && e->d_wd[j]) {          // the flipped kernel (Cin, 3 Cout): K = 3 Cout must be whole 16-k groups
             t.wp[t.count] = e->d_wd[j]; t.hm[t.count] = e->d_wdhm[j]; t.wl[t.count] = e->d_wdl[j]; t.n8[t.count] = n / 8; t.K[t.count] = 3 * e->geom[j].Cout; ++t.count;
         }
     }
-    { int rcs = launch_split_weights_multi(t, st); if (rcs != NAFP_OK) return rcs; }
+    return launch_split_weights_multi(t, st);
+}
+static int split_all_weights(nafp_encoder* e, hipStream_t st) {
+    { int rcs = split_weights(e, st, 1, 15); if (rcs != NAFP_OK) return rcs; }
     e->x6_dirty = false;
     return NAFP_OK;
 }
@@ -414,10 +421,11 @@ extern "C" int nafp_encoder_set_option(nafp_encoder* e, int option, int value) {
             e->opt_fused_ln_bwd = value; return NAFP_OK;
         case NAFP_OPT_BWD_OVERLAP: e->opt_bwd_overlap = value < 0 ? 0 : (value > 2 ? 1 : value); return NAFP_OK;
         case NAFP_OPT_SMALLNET: return NAFP_OK;          // retired in round 6 (the persistent small-layer launch lost to the per-layer launches at every setting): accepted, ignored
-        case NAFP_OPT_DEBUG_SIDE_DELAY: {     // test hook, not in include/nafp.h: refused outside a test process (round-5 ADVICE)
+        case NAFP_OPT_DEBUG_SIDE_DELAY:       // test hooks, not in include/nafp.h: refused outside a test process (round-5 ADVICE)
+        case NAFP_OPT_DEBUG_SW_DELAY: {
             static const bool hooks = []() { const char* v = getenv("NAFP_TEST_HOOKS"); return v && v[0] == '1'; }();
             if (!hooks) return NAFP_ERR_UNSUPPORTED;
-            e->debug_side_delay_us = value < 0 ? 0 : value; return NAFP_OK;
+            (option == NAFP_OPT_DEBUG_SIDE_DELAY ? e->debug_side_delay_us : e->debug_sw_delay_us) = value < 0 ? 0 : value; return NAFP_OK;
         }
         default: return NAFP_ERR_INVALID_ARG;
     }
@@ -493,6 +501,18 @@ extern "C" int nafp_encoder_set_weights(nafp_encoder* e, const float* const* t, 
         if (rcx != NAFP_OK) return rcx;
     }
     NAFP_HIP_CHECK(hipEventRecord(e->sw_copied, st));
+    // test hook (NAFP_OPT_DEBUG_SW_DELAY): the caller's stream idles behind each early event, so that a pass on another stream that
+    // waits for an early event but reads something written after it reads stale data every time, not by chance
+    auto sw_delay = [&]() -> int {
+        if (e->debug_sw_delay_us <= 0) return NAFP_OK;
+        debug_delay_kernel<<<1, 64, 0, st>>>((long long)e->debug_sw_delay_us);
+        NAFP_LAUNCH_CHECK();
+        return NAFP_OK;
+    };
+    { int rcd = sw_delay(); if (rcd != NAFP_OK) return rcd; }
+    // (experimental, NAFP_OPT_BF16X3 = 2) the training forward's conv1 also reads layer 1's three bf16 terms: they are split in
+    // front of `sw_l1` (either record below), the other layers' in front of `sw_done`
+    auto split_l1 = [&]() -> int { return e->opt_bf16x3 == 2 ? split_weights(e, st, 1, 1) : NAFP_OK; };
     {
         PackTable pt; pt.count = 0; pt.nonfinite = e->d_wflag;
         for (int j = 1; j < 16; ++j) {
@@ -530,7 +550,9 @@ extern "C" int nafp_encoder_set_weights(nafp_encoder* e, const float* const* t, 
         add_bias_kernel<<<dim3(32, 1), 256, 0, st>>>(b1);
         NAFP_LAUNCH_CHECK();
         l1_done = true;
+        { int rcs = split_l1(); if (rcs != NAFP_OK) return rcs; }
         NAFP_HIP_CHECK(hipEventRecord(e->sw_l1, st));
+        { int rcd = sw_delay(); if (rcd != NAFP_OK) return rcd; }
     }
     NAFP_HIP_CHECK(hipEventRecord(e->sw_fork, st));                         // copies and re-packs above are done
     // Between the fork and the join nothing returns early: whatever fails, the helper streams are joined back into the
@@ -577,11 +599,16 @@ extern "C" int nafp_encoder_set_weights(nafp_encoder* e, const float* const* t, 
     NAFP_LAUNCH_CHECK();
     int rc = launch_pack_div(t[64], t[65], t[66], e->d_w1p, e->d_b1p, e->d_w2p, e->emb_sz, e->S, st);
     if (rc != NAFP_OK) return rc;
-    if (!l1_done) NAFP_HIP_CHECK(hipEventRecord(e->sw_l1, st));
+    if (!l1_done) {
+        { int rcs = split_l1(); if (rcs != NAFP_OK) return rcs; }
+        NAFP_HIP_CHECK(hipEventRecord(e->sw_l1, st));
+        { int rcd = sw_delay(); if (rcd != NAFP_OK) return rcd; }
+    }
     e->x6_dirty = true;
-    if (e->opt_bf16x3 == 2) {                 // (experimental) the exact-split kernels' three bf16 terms of every packed conv kernel: part of this call,
-        int rcs = split_all_weights(e, st);   //  so that `sw_done` covers them for passes on other streams
+    if (e->opt_bf16x3 == 2) {                 // (experimental) the exact-split kernels' three bf16 terms of the other packed conv kernels: part of
+        int rcs = split_weights(e, st, 2, 15);  //  this call, so that `sw_done` covers them for passes on other streams
         if (rcs != NAFP_OK) return rcs;
+        e->x6_dirty = false;
     }
     NAFP_HIP_CHECK(hipEventRecord(e->sw_done, st));
     e->sw_stream = st; e->sw_recorded = true;

@@ -2161,8 +2161,8 @@ int launch_conv_gemm(const ConvGemmArgs& a, int64_t B, const ConvGeom& g, hipStr
              : bn == 64 ? launch_variant(conv_gemm_n64k16s2_infer_bf16x6, 128, 64, 16, 2, p, grid, st, 64 * 8)
                         : launch_variant(conv_gemm_k16s3_infer_bf16x6, 128, 128, 16, NAFP_X6_K16_NSTAGE, p, grid, st, 128 * 8);
     }
-    // the training epilogue on the exact split (x6 forces 128-row tiles; launches that need the generic-statistics or the in-kernel-finish
-    // epilogue -- the small late layers -- stay on the f32 kernels)
+    // the training epilogue on the exact split (x6 forces 128-row tiles), and the generic-statistics epilogue (samples per position other
+    // than 4 / 8: the small late layers of a large training batch); launches that need the in-kernel-finish epilogue stay on the f32 kernels
     static const bool x6_any = []() { const char* e = getenv("NAFP_X6_ANY"); return !e || e[0] != '0'; }();      // (A/B knob)
     if (x6 && epi == 2 && BM == 128 && x6_any) {
         p.wp_hm = a.wp_hm; p.wp_l = (const unsigned short*)a.wp_l;

@@ -184,13 +184,15 @@ def test_train_step_with_other_embedding_widths(nafp, cfg, emb_sz):
     assert all(np.isfinite(losses)) and losses[-1] < losses[0]
 
 
-def test_prefetched_weight_repack_equals_the_lazy_one(nafp, cfg, monkeypatch):
+def test_prefetched_weight_repack_equals_the_lazy_one(nafp, cfg, monkeypatch, arith):
     """`train_step` starts the re-pack of the updated weights on a stream of the handle's own right after the optimizer
     (`FingerPrinter.prefetch_weights`); the next passes wait INSIDE the library for the part of it they read (the training forward:
     plain copies -> conv0, layer 1's share -> conv1, everything -> conv2; any other pass: everything).  Five steps with the
     prefetch and five with the lazy re-pack at the next forward (same seeded data, no spec-augment) must give the same
     losses and variables to the rounding of the backward pass's atomics -- and a forward issued on ANOTHER stream right
-    after a step must see the new weights, not the old blob."""
+    after a step must see the new weights, not the old blob.  Under both arithmetics: with `arith` = x6 the re-pack also splits
+    every packed kernel into its three bf16 terms, which conv1 of the training forward reads behind layer 1's event
+    (tests/test_gpu_weight_ordering.py holds that ordering with the re-pack delayed on purpose)."""
     from neural_audio_fp_amd.model import trainer as T
     from neural_audio_fp_amd.model.fp.lamb_optimizer import LAMB
     from neural_audio_fp_amd.model.fp.NTxent_loss_single_gpu import NTxentLoss
@@ -203,6 +205,7 @@ def test_prefetched_weight_repack_equals_the_lazy_one(nafp, cfg, monkeypatch):
     for prefetch in (True, False):
         monkeypatch.setattr(T, '_PREFETCH_WEIGHTS', prefetch)
         m_fp = nafp.FingerPrinter(seed=0)
+        assert m_fp.split_arithmetic == (2 if arith == 'x6' else 0)
         m_fp.set_weights(_inputs.weight_list(_inputs.weights(seed=22)))
         opt = LAMB(learning_rate=1e-3)
         loss_obj = NTxentLoss(n_org=n, n_rep=n, tau=0.05)

@@ -466,6 +466,70 @@ int nafp_search_seq_scores(const float* query, const float* index, int64_t n_ind
                            const int32_t* task_q0, const int32_t* task_len, int64_t n_tasks,
                            const int32_t* cand, int n_slots, float* out_scores, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Approximate indexes: IVF-Flat and IVF-PQ (faiss IndexIVFFlat / IndexIVFPQ as
+ * eval/utils/get_index_faiss.py:64-80 builds them; opt-in from eval_faiss.py).  Building blocks of
+ * training and add (bucketing, k-means update, PQ encoding) and the two searches.  dim 64 / 128 / 256;
+ * PQ: M = 64 sub-quantizers of 256 codewords (pq_centroids (M, 256, dim / M) float32), codes (n, M) uint8.
+ * Ties everywhere: the smaller id (list, code, row) first.  All pointers are device pointers; results
+ * are bit-identical from run to run and do not depend on how rows or queries are batched.
+ * Status: NAFP_ERR_INVALID_ARG for a null pointer or a negative size, NAFP_ERR_UNSUPPORTED for a dim
+ * outside 64 / 128 / 256, k > 32, nprobe > 128, M != 64 or n_buckets / nlist > 16384; checked before
+ * any GPU call.  The *_workspace_bytes queries return -1 for such arguments.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Stable counting sort of `batch` key arrays: key (b, i) = keys[i * batch + b] (int32 or uint8 by
+ * key_bytes), 0 <= key < n_buckets (others are dropped).  offsets (batch, n_buckets + 1): bucket starts;
+ * ids (batch, n): item ids i grouped by key, ascending inside a bucket. */
+int64_t nafp_ivf_bucket_workspace_bytes(int64_t n, int n_buckets, int batch);
+int nafp_ivf_bucket(const void* keys, int key_bytes, int64_t n, int n_buckets, int batch, int32_t* offsets,
+                    int32_t* ids, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* k-means update on bucketed points: sort b (of batch) covers coordinates [b * dim / batch, (b + 1) *
+ * dim / batch) of the rows x (n, dim); centroids (batch, n_buckets, dim / batch) of non-empty buckets
+ * become the mean of their points (summed in id order, in double); empty ones are left as they are.
+ * counts (batch, n_buckets) receives the bucket sizes. */
+int nafp_ivf_kmeans_update(const float* x, int64_t n, int dim, int batch, const int32_t* offsets,
+                           const int32_t* ids, int n_buckets, float* centroids, int32_t* counts, void* stream);
+
+/* out (n, dim) = x - centroids[assign] */
+int nafp_ivf_residuals(const float* x, int64_t n, int dim, const int32_t* assign, const float* centroids,
+                       float* out, void* stream);
+
+/* codes (n, M): per sub-space the nearest codeword of x - coarse[assign] (assign and coarse both NULL:
+ * of x itself). */
+int nafp_ivf_pq_encode(const float* x, int64_t n, int dim, const int32_t* assign, const float* coarse,
+                       const float* pq_centroids, int M, uint8_t* codes, void* stream);
+
+/* probe (n_query, nprobe): the nprobe nearest of nlist centroids per query, nearest first (nprobe <= nlist). */
+int nafp_ivf_probe(const float* query, int64_t n_query, const float* centroids, int nlist, int dim, int nprobe,
+                   int32_t* probe, void* stream);
+
+/* IVF-Flat list storage: rows (bound, dim), half_norms (bound), row_ids (bound) with bound =
+ * nafp_ivf_flat_rows_bound(n, nlist); list l holds rows [row_offsets[l], row_offsets[l + 1]) (nlist + 1
+ * entries), padded to whole 64-row tiles (row id -1).  offsets / ids: nafp_ivf_bucket of the rows' lists. */
+int64_t nafp_ivf_flat_rows_bound(int64_t n, int nlist);
+int nafp_ivf_flat_lists(const float* x, int64_t n, int dim, const int32_t* offsets, const int32_t* ids, int nlist,
+                        int32_t* row_offsets, float* rows, float* half_norms, int32_t* row_ids, void* stream);
+/* IVF-PQ list storage: codes_sorted[p] = codes[ids[p]] (n rows of M bytes). */
+int nafp_ivf_pq_lists(const uint8_t* codes, int64_t n, int M, const int32_t* ids, uint8_t* codes_sorted,
+                      void* stream);
+
+/* kind 0: IVF-Flat, 1: IVF-PQ.  nprobe is clamped to nlist. */
+int64_t nafp_ivf_search_workspace_bytes(int64_t n_query, int nlist, int nprobe, int k, int kind);
+/* out_dist / out_ids (n_query, k): the k nearest rows of the nprobe nearest lists; exact fp32 squared L2
+ * distances; fewer than k rows: id -1, distance +inf. */
+int nafp_ivf_flat_search(const float* query, int64_t n_query, const float* centroids, int nlist, int dim,
+                         int nprobe, const float* rows, const float* half_norms, const int32_t* row_offsets,
+                         const int32_t* row_ids, int k, float* out_dist, int32_t* out_ids, void* workspace,
+                         int64_t workspace_bytes, void* stream);
+/* The same with the fp32 ADC distance sum_m |(q - c_list)_m - P[m][code_m]|^2 (codes_sorted / offsets /
+ * ids: the lists as nafp_ivf_pq_lists and nafp_ivf_bucket leave them). */
+int nafp_ivf_pq_search(const float* query, int64_t n_query, const float* centroids, int nlist, int dim, int nprobe,
+                       const float* pq_centroids, int M, const uint8_t* codes_sorted, const int32_t* offsets,
+                       const int32_t* ids, int k, float* out_dist, int32_t* out_ids, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+
 /* In-training mini search test (model/utils/mini_search_subroutines.py): pairwise_distances_for_eval (:28-93;
  * mode 0 = squared L2 clipped at 0 for 'argmin', 1 = dot product for 'argmax'; any dim) into out_scores
  * (n_query, n_db); then, per sequence length `scope`, the rank of the ground-truth start id

@@ -89,6 +89,21 @@ PROTOTYPES = {
                                     c_void_p, c_i64, c_void_p]),
     'nafp_search_seq_scores': (c_int, [c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_int,
                                        c_void_p, c_void_p]),
+    'nafp_ivf_bucket_workspace_bytes': (c_i64, [c_i64, c_int, c_int]),
+    'nafp_ivf_bucket': (c_int, [c_void_p, c_int, c_i64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    'nafp_ivf_kmeans_update': (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    'nafp_ivf_residuals': (c_int, [c_void_p, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'nafp_ivf_pq_encode': (c_int, [c_void_p, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'nafp_ivf_probe': (c_int, [c_void_p, c_i64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'nafp_ivf_flat_rows_bound': (c_i64, [c_i64, c_int]),
+    'nafp_ivf_flat_lists': (c_int, [c_void_p, c_i64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p]),
+    'nafp_ivf_pq_lists': (c_int, [c_void_p, c_i64, c_int, c_void_p, c_void_p, c_void_p]),
+    'nafp_ivf_search_workspace_bytes': (c_i64, [c_i64, c_int, c_int, c_int, c_int]),
+    'nafp_ivf_flat_search': (c_int, [c_void_p, c_i64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                     c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    'nafp_ivf_pq_search': (c_int, [c_void_p, c_i64, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                   c_int, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
     'nafp_minisearch_scores': (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_void_p, c_void_p]),
     'nafp_minisearch_ranks': (c_int, [c_void_p, c_i64, c_i64, c_int, c_int, c_int, c_void_p, c_void_p]),
     'nafp_lamb_step': (c_int, [c_void_p, c_int, c_float, c_float, c_float, c_float, c_float, c_i64,

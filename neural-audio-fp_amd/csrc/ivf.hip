@@ -1,0 +1,663 @@
+// Approximate indexes: IVF-Flat and IVF-PQ (faiss IndexIVFFlat / IndexIVFPQ as eval/utils/get_index_faiss.py:64-80 builds
+// them), gfx950.  Opt-in from eval/eval_faiss.py (NAFP_APPROX_INDEX=1); the host side is eval/ivf.py.
+//
+//   ivf_bucket_{count,scan_tiles,offsets,scatter}_kernel   stable counting sort of item ids by key (histogram per 4096-item
+//                              tile, scan over tiles per bucket, scan over buckets, scatter).  The scatter keeps ascending ids
+//                              inside a bucket: one wave per tile walks its items in order, 64 at a time, and ranks equal keys
+//                              inside the 64 by ballots over the key bits -- no atomic slot claims.  Serves the inverted lists
+//                              (rows by list), the k-means update (training points by cluster) and the search ((query, probe)
+//                              pairs by list).  `batch` independent sorts at once (the M sub-quantizers of PQ training).
+//   ivf_kmeans_update_kernel   centroid = mean of its bucketed points, summed in bucket (= ascending id) order in double:
+//                              no float atomics, so training is bit-reproducible
+//   ivf_pq_encode_kernel<DSUB> residual to the assigned coarse centroid, then per sub-space the nearest of 256 codewords
+//                              (equal distances: the smaller code); the codebooks of 64 / DSUB sub-spaces (64 KB) sit in LDS,
+//                              blockIdx.y walks the sub-space groups (d = 128: 128 KB of codebooks, 2 groups; d = 256: 4)
+//   ivf_probe_kernel           per query the nprobe nearest coarse centroids (exact fp32 |q - c|^2; rank by counting, ties:
+//                              smaller list id)
+//   ivf_flat_lists_kernel      the lists' rows copied contiguously, each list padded to whole 64-row tiles (+inf half norms)
+//   ivf_flat_scan_kernel       (search.hip) the exact search's fp32-MFMA body over one list for the queries probing it
+//   ivf_pq_scan_kernel<DSUB,K> per (query, list) pair: the fp32 ADC table (64 x 256, 64 KB of LDS), then the list's 64-byte
+//                              codes, 64 LDS lookups per row, summed in sub-space order; register top-K per lane, then a
+//                              workgroup-wide K-way selection
+//   ivf_merge_kernel           per query: the probes' partial lists -> k results (distance asc, id asc), -1 / +inf padding
+#include "nafp_common.h"
+
+#include <algorithm>
+
+namespace nafp {
+
+int ivf_flat_scan_launch(int D, int K, unsigned grid_x, int parts, const float* Q, const int* qmap, const int* pair_off,
+                         const int* qblk_off, int nlist, const float* Xs, const float* hns, const int* row_off, float* pk, int* pi,
+                         hipStream_t st);                                     // search.hip
+
+constexpr int BUCKET_TILE = 4096;           // items per wave in the bucketing kernels
+constexpr int IVF_MAX_BUCKETS = 16384;      // one int per bucket in LDS (64 KB)
+constexpr int IVF_MAX_CANDS = 16384;        // partial results per query in the merge (128 KB of LDS)
+constexpr int PQ_KS = 256;                  // codewords per sub-space (nbits = 8)
+constexpr int PQ_M = 64;                    // sub-quantizers
+
+__device__ __forceinline__ unsigned long long ivf_pack(float key, int id) {
+    unsigned u = __float_as_uint(key);
+    u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;                              // order-preserving map
+    return ((unsigned long long)u << 32) | (unsigned)(0x7fffffff - id);       // ties: smaller id is larger
+}
+__device__ __forceinline__ float ivf_unpack_key(unsigned long long v) {
+    unsigned u = (unsigned)(v >> 32);
+    u = (u >> 31) ? (u ^ 0x80000000u) : ~u;
+    return __uint_as_float(u);
+}
+__device__ __forceinline__ int ivf_unpack_id(unsigned long long v) { return 0x7fffffff - (int)(unsigned)(v & 0xffffffffull); }
+
+template <typename KT>
+__device__ __forceinline__ int bucket_key(const KT* keys, int64_t i, int batch, int b) { return (int)keys[i * batch + b]; }
+
+// ---- stable counting sort ------------------------------------------------------------------------------------------
+template <typename KT>
+__global__ __launch_bounds__(64) void ivf_bucket_count_kernel(const KT* __restrict__ keys, int64_t n, int nb, int batch,
+                                                              int* __restrict__ tile_counts, int n_tiles) {
+    extern __shared__ int cnt[];
+    const int lane = threadIdx.x, t = blockIdx.x, b = blockIdx.y;
+    for (int j = lane; j < nb; j += 64) cnt[j] = 0;
+    __syncthreads();
+    const int64_t i0 = (int64_t)t * BUCKET_TILE, i1 = std::min<int64_t>(n, i0 + BUCKET_TILE);
+    for (int64_t i = i0 + lane; i < i1; i += 64) {
+        const int k = bucket_key(keys, i, batch, b);
+        if ((unsigned)k < (unsigned)nb) atomicAdd(&cnt[k], 1);               // integer counts: order-free
+    }
+    __syncthreads();
+    int* out = tile_counts + ((int64_t)b * n_tiles + t) * nb;
+    for (int j = lane; j < nb; j += 64) out[j] = cnt[j];
+}
+
+// per (batch, bucket): exclusive prefix over the tiles in place, total into totals
+__global__ __launch_bounds__(256) void ivf_bucket_scan_tiles_kernel(int* __restrict__ tile_counts, int n_tiles, int nb,
+                                                                    int* __restrict__ totals) {
+    const int j = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+    if (j >= nb) return;
+    int* c = tile_counts + (int64_t)b * n_tiles * nb + j;
+    int run = 0;
+    for (int t = 0; t < n_tiles; ++t) { const int v = c[(int64_t)t * nb]; c[(int64_t)t * nb] = run; run += v; }
+    totals[(int64_t)b * nb + j] = run;
+}
+
+// per batch: offsets[0..nb] = exclusive prefix of the totals
+__global__ __launch_bounds__(256) void ivf_bucket_offsets_kernel(const int* __restrict__ totals, int nb, int* __restrict__ offsets) {
+    __shared__ int part[256];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int chunk = (nb + 255) / 256, j0 = std::min(nb, tid * chunk), j1 = std::min(nb, j0 + chunk);
+    const int* tt = totals + (int64_t)b * nb;
+    int s = 0;
+    for (int j = j0; j < j1; ++j) s += tt[j];
+    part[tid] = s;
+    __syncthreads();
+    if (tid == 0) {
+        int run = 0;
+        for (int i = 0; i < 256; ++i) { const int v = part[i]; part[i] = run; run += v; }
+        offsets[(int64_t)b * (nb + 1) + nb] = run;
+    }
+    __syncthreads();
+    int run = part[tid];
+    for (int j = j0; j < j1; ++j) { offsets[(int64_t)b * (nb + 1) + j] = run; run += tt[j]; }
+}
+
+template <typename KT>
+__global__ __launch_bounds__(64) void ivf_bucket_scatter_kernel(const KT* __restrict__ keys, int64_t n, int nb, int batch,
+                                                                const int* __restrict__ tile_prefix, const int* __restrict__ offsets,
+                                                                int* __restrict__ ids, int n_tiles, int nbits) {
+    extern __shared__ int base[];
+    const int lane = threadIdx.x, t = blockIdx.x, b = blockIdx.y;
+    const int* tp = tile_prefix + ((int64_t)b * n_tiles + t) * nb;
+    const int* of = offsets + (int64_t)b * (nb + 1);
+    for (int j = lane; j < nb; j += 64) base[j] = of[j] + tp[j];
+    __syncthreads();
+    const int64_t i0 = (int64_t)t * BUCKET_TILE, i1 = std::min<int64_t>(n, i0 + BUCKET_TILE);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int* out = ids + (int64_t)b * n;
+    for (int64_t c0 = i0; c0 < i1; c0 += 64) {                    // items in order, 64 at a time (one wave: lockstep)
+        const int64_t i = c0 + lane;
+        int k = i < i1 ? bucket_key(keys, i, batch, b) : -1;
+        const bool valid = (unsigned)k < (unsigned)nb;
+        unsigned long long same = __ballot(valid);
+        for (int bit = 0; bit < nbits; ++bit) {                   // lanes with the same key: agree on every key bit
+            const bool v = (k >> bit) & 1;
+            const unsigned long long bb = __ballot(valid && v);
+            same &= v ? bb : ~bb;
+        }
+        if (valid) {
+            const int slot = base[k] + __popcll(same & below);
+            out[slot] = (int)i;
+            if ((same >> lane) == 1ull) base[k] += __popcll(same);    // the last lane of the group moves the bucket's cursor
+        }
+        __syncthreads();
+    }
+}
+
+// ---- k-means update ------------------------------------------------------------------------------------------------
+// cluster c of sort b: points ids[b][offsets[c] .. offsets[c+1]), coordinates x[i * dim + b * dsub + dd]
+__global__ __launch_bounds__(64) void ivf_kmeans_update_kernel(const float* __restrict__ x, int64_t n, int dim, int dsub,
+                                                               const int* __restrict__ offsets, const int* __restrict__ ids,
+                                                               int nb, float* __restrict__ cent, int* __restrict__ counts) {
+    const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int* of = offsets + (int64_t)b * (nb + 1);
+    const int o0 = of[c], o1 = of[c + 1];
+    if (tid == 0) counts[(int64_t)b * nb + c] = o1 - o0;
+    if (o1 == o0) return;                                         // empty: the host splits a donor into it
+    const int* id = ids + (int64_t)b * n;
+    for (int dd = tid; dd < dsub; dd += 64) {
+        double s = 0.0;
+        for (int p = o0; p < o1; ++p) s += (double)x[(int64_t)id[p] * dim + b * dsub + dd];
+        cent[((int64_t)b * nb + c) * dsub + dd] = (float)(s / (double)(o1 - o0));
+    }
+}
+
+__global__ __launch_bounds__(256) void ivf_residual_kernel(const float* __restrict__ x, int64_t n, int dim,
+                                                           const int* __restrict__ assign, const float* __restrict__ cent,
+                                                           float* __restrict__ out) {
+    const int64_t e = blockIdx.x * 256ll + threadIdx.x;
+    if (e >= n * dim) return;
+    const int64_t i = e / dim;
+    const int dd = (int)(e - i * dim);
+    out[e] = x[e] - cent[(int64_t)assign[i] * dim + dd];
+}
+
+// ---- PQ encode -----------------------------------------------------------------------------------------------------
+template <int DSUB>
+__global__ __launch_bounds__(256) void ivf_pq_encode_kernel(const float* __restrict__ x, int64_t n, const int* __restrict__ assign,
+                                                            const float* __restrict__ coarse, const float* __restrict__ pq,
+                                                            unsigned char* __restrict__ codes) {
+    constexpr int D = PQ_M * DSUB, MG = PQ_M / DSUB;             // sub-spaces per workgroup: 64 KB of codebooks
+    __shared__ float cb[MG * PQ_KS * DSUB];
+    const int tid = threadIdx.x, m0 = blockIdx.y * MG;
+    for (int e = tid; e < MG * PQ_KS * DSUB; e += 256) cb[e] = pq[(int64_t)m0 * PQ_KS * DSUB + e];
+    __syncthreads();
+    const int64_t i = blockIdx.x * 256ll + tid;
+    if (i >= n) return;
+    const float* xr = x + i * D;
+    const float* cr = assign ? coarse + (int64_t)assign[i] * D : nullptr;
+    for (int mm = 0; mm < MG; ++mm) {
+        const int m = m0 + mm;
+        float r[DSUB];
+#pragma unroll
+        for (int u = 0; u < DSUB; ++u) r[u] = cr ? xr[m * DSUB + u] - cr[m * DSUB + u] : xr[m * DSUB + u];
+        float best = INFINITY;
+        int bj = 0;
+        const float* c = cb + mm * PQ_KS * DSUB;
+        for (int j = 0; j < PQ_KS; ++j) {
+            float s = 0.f;
+#pragma unroll
+            for (int u = 0; u < DSUB; ++u) { const float t = r[u] - c[j * DSUB + u]; s += t * t; }
+            if (s < best) { best = s; bj = j; }
+        }
+        codes[i * PQ_M + m] = (unsigned char)bj;
+    }
+}
+
+// ---- probe selection -----------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void ivf_probe_kernel(const float* __restrict__ Q, const float* __restrict__ cent, int nlist,
+                                                        int dim, int nprobe, int* __restrict__ probe) {
+    extern __shared__ float sm[];                                 // [dim] query, [nlist] distances
+    float* qs = sm;
+    float* dist = sm + dim;
+    const int64_t q = blockIdx.x;
+    const int tid = threadIdx.x;
+    for (int dd = tid; dd < dim; dd += 256) qs[dd] = Q[q * dim + dd];
+    __syncthreads();
+    for (int c = tid; c < nlist; c += 256) {
+        const float* cr = cent + (int64_t)c * dim;
+        float s = 0.f;
+        for (int dd = 0; dd < dim; ++dd) { const float t = qs[dd] - cr[dd]; s += t * t; }
+        dist[c] = s;
+    }
+    __syncthreads();
+    for (int c = tid; c < nlist; c += 256) {
+        const float dc = dist[c];
+        int r = 0;
+        for (int c2 = 0; c2 < nlist; ++c2) { const float d2 = dist[c2]; r += (d2 < dc || (d2 == dc && c2 < c)) ? 1 : 0; }
+        if (r < nprobe) probe[q * nprobe + r] = c;
+    }
+}
+
+// ---- list storage --------------------------------------------------------------------------------------------------
+// row_off[l] = sum over l' < l of the list lengths rounded up to whole tiles
+__global__ void ivf_padded_offsets_kernel(const int* __restrict__ off, int nlist, int* __restrict__ row_off) {
+    if (threadIdx.x != 0) return;
+    int run = 0;
+    for (int l = 0; l < nlist; ++l) { row_off[l] = run; run += (off[l + 1] - off[l] + 63) / 64 * 64; }
+    row_off[nlist] = run;
+}
+
+__device__ __forceinline__ int ivf_find_list(const int* __restrict__ off, int nlist, int64_t p) {
+    int lo = 0, hi = nlist;                                       // the largest l with off[l] <= p
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (off[mid] <= p) lo = mid; else hi = mid; }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void ivf_flat_lists_kernel(const float* __restrict__ x, int dim, const int* __restrict__ off,
+                                                             const int* __restrict__ ids, int nlist, const int* __restrict__ row_off,
+                                                             int64_t bound, float* __restrict__ xs, float* __restrict__ hn,
+                                                             int* __restrict__ row_ids) {
+    const int64_t p = blockIdx.x * 256ll + threadIdx.x;
+    if (p >= bound || p >= row_off[nlist]) return;
+    const int l = ivf_find_list(row_off, nlist, p);
+    const int64_t local = p - row_off[l];
+    float4* dst = (float4*)(xs + p * dim);
+    if (local < off[l + 1] - off[l]) {
+        const int src = ids[off[l] + local];
+        const float4* r = (const float4*)(x + (int64_t)src * dim);
+        float s = 0.f;                                            // search_half_norms_kernel's order
+        for (int c = 0; c < dim / 4; ++c) { const float4 v = r[c]; dst[c] = v; s += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w); }
+        hn[p] = 0.5f * s;
+        row_ids[p] = src;
+    } else {
+        for (int c = 0; c < dim / 4; ++c) dst[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+        hn[p] = INFINITY;
+        row_ids[p] = -1;
+    }
+}
+
+__global__ __launch_bounds__(256) void ivf_gather_codes_kernel(const uint4* __restrict__ codes, const int* __restrict__ ids, int64_t n,
+                                                               uint4* __restrict__ out) {
+    const int64_t e = blockIdx.x * 256ll + threadIdx.x;            // PQ_M / 16 = 4 uint4 per row
+    if (e >= n * 4) return;
+    out[e] = codes[(int64_t)ids[e >> 2] * 4 + (e & 3)];
+}
+
+// ---- search --------------------------------------------------------------------------------------------------------
+// pos = position of pair e = (query e / np, probe e % np) in list order
+__global__ __launch_bounds__(256) void ivf_pairs_kernel(const int* __restrict__ sorted, const int* __restrict__ probe, int64_t n_pairs,
+                                                        int np, int* __restrict__ qmap, int* __restrict__ plist, int* __restrict__ inv) {
+    const int64_t pos = blockIdx.x * 256ll + threadIdx.x;
+    if (pos >= n_pairs) return;
+    const int e = sorted[pos];
+    qmap[pos] = e / np;
+    plist[pos] = probe[e];
+    inv[e] = (int)pos;
+}
+
+__global__ void ivf_qblock_prefix_kernel(const int* __restrict__ pair_off, int nlist, int* __restrict__ qblk_off) {
+    if (threadIdx.x != 0) return;
+    int run = 0;
+    for (int l = 0; l < nlist; ++l) { qblk_off[l] = run; run += (pair_off[l + 1] - pair_off[l] + 127) / 128; }
+    qblk_off[nlist] = run;
+}
+
+// one workgroup per (pair, part): ADC table of the pair in LDS, then rows [r0, r1) of the list's part
+template <int DSUB, int K>
+__global__ __launch_bounds__(256) void ivf_pq_scan_kernel(const float* __restrict__ Q, const int* __restrict__ qmap,
+                                                          const int* __restrict__ plist, const float* __restrict__ coarse,
+                                                          const float* __restrict__ pq, const unsigned char* __restrict__ codes,
+                                                          const int* __restrict__ off, const int* __restrict__ ids, int parts,
+                                                          float* __restrict__ pk, int* __restrict__ pi) {
+    constexpr int D = PQ_M * DSUB, NT = PQ_M * PQ_KS;
+    extern __shared__ __attribute__((aligned(16))) float lut[];   // [NT] table, then [D] residual, [4] x u64 wave bests
+    float* rr = lut + NT;
+    unsigned long long* wbest = (unsigned long long*)(rr + 256);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t pos = blockIdx.x;
+    const int part = blockIdx.y;
+    const int q = qmap[pos], l = plist[pos];
+    for (int dd = tid; dd < D; dd += 256) rr[dd] = Q[(int64_t)q * D + dd] - coarse[(int64_t)l * D + dd];
+    __syncthreads();
+    for (int e = tid; e < NT; e += 256) {
+        const int m = e >> 8;
+        const float* c = pq + (int64_t)e * DSUB;
+        float s = 0.f;
+#pragma unroll
+        for (int u = 0; u < DSUB; ++u) { const float t = rr[m * DSUB + u] - c[u]; s += t * t; }
+        lut[e] = s;
+    }
+    __syncthreads();
+    const int o0 = off[l];
+    const int len = off[l + 1] - o0;
+    const int per = (len + parts - 1) / parts;
+    const int r0 = std::min(len, part * per), r1 = std::min(len, r0 + per);
+    float sc[K]; int id[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) { sc[j] = -INFINITY; id[j] = -1; }
+    // the next row's codes are loaded before this row's lookups (they come from L2 / MALL; 8 waves per CU hide little)
+    uint4 n0 = make_uint4(0u, 0u, 0u, 0u), n1 = n0, n2 = n0, n3 = n0;
+    if (r0 + tid < r1) {
+        const uint4* cp = (const uint4*)(codes + (int64_t)(o0 + r0 + tid) * PQ_M);
+        n0 = cp[0]; n1 = cp[1]; n2 = cp[2]; n3 = cp[3];
+    }
+    for (int r = r0 + tid; r < r1; r += 256) {
+        const uint4 w0 = n0, w1 = n1, w2 = n2, w3 = n3;
+        if (r + 256 < r1) {
+            const uint4* cp = (const uint4*)(codes + (int64_t)(o0 + r + 256) * PQ_M);
+            n0 = cp[0]; n1 = cp[1]; n2 = cp[2]; n3 = cp[3];
+        }
+        const unsigned w[16] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w, w3.x, w3.y, w3.z, w3.w};
+        float s = 0.f;
+#pragma unroll
+        for (int m = 0; m < PQ_M; ++m) s += lut[m * PQ_KS + ((w[m >> 2] >> (8 * (m & 3))) & 255u)];
+        const float key = -s;
+        if (key > sc[K - 1]) {                                    // rows ascend within the lane: ties keep the smaller id
+            const int nid = ids[o0 + r];
+#pragma unroll
+            for (int j = K - 1; j >= 1; --j) {
+                const bool cj = key > sc[j], cp2 = key > sc[j - 1];
+                id[j] = cj ? (cp2 ? id[j - 1] : nid) : id[j];
+                sc[j] = cj ? (cp2 ? sc[j - 1] : key) : sc[j];
+            }
+            if (key > sc[0]) { sc[0] = key; id[0] = nid; }
+        }
+    }
+    // workgroup top-K: the 256 sorted lane lists in LDS (the table is done), K rounds of a workgroup-wide arg-max of the heads
+    __syncthreads();
+    unsigned long long* cl = (unsigned long long*)lut;
+#pragma unroll
+    for (int j = 0; j < K; ++j) cl[tid * K + j] = id[j] >= 0 ? ivf_pack(sc[j], id[j]) : 0ull;
+    __syncthreads();
+    int h = 0;
+    const int64_t o = (pos * parts + part) * K;
+    for (int j = 0; j < K; ++j) {
+        const unsigned long long v = h < K ? cl[tid * K + h] : 0ull;
+        unsigned long long b = v;
+#pragma unroll
+        for (int s2 = 32; s2 > 0; s2 >>= 1) { const unsigned long long ob = __shfl_xor(b, s2, 64); b = ob > b ? ob : b; }
+        if (lane == 0) wbest[wave] = b;
+        __syncthreads();
+        unsigned long long best = wbest[0];
+        for (int w2 = 1; w2 < 4; ++w2) best = wbest[w2] > best ? wbest[w2] : best;
+        if (best != 0ull && v == best) ++h;
+        if (tid == 0) {
+            pk[o + j] = best ? ivf_unpack_key(best) : -INFINITY;
+            pi[o + j] = best ? ivf_unpack_id(best) : -1;
+        }
+        __syncthreads();
+    }
+}
+
+// one wave per query: the np x slots x K partial results of its probes -> k_out results.  mode 0 (flat): keys are
+// q.x - |x|^2/2 with list-relative row ids (mapped through row_ids); mode 1 (PQ): keys are -distance with global ids.
+__global__ __launch_bounds__(64) void ivf_merge_kernel(const float* __restrict__ pk, const int* __restrict__ pi,
+                                                       const int* __restrict__ inv, const int* __restrict__ probe, int np, int slotsK,
+                                                       const int* __restrict__ row_ids, const int* __restrict__ row_off,
+                                                       const float* __restrict__ Q, int D, int mode, float* __restrict__ out_dist,
+                                                       int* __restrict__ out_ids, int k_out) {
+    extern __shared__ unsigned long long cand[];
+    const int64_t q = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int M = np * slotsK;
+    for (int i = lane; i < M; i += 64) {
+        const int p = i / slotsK, s = i - p * slotsK;
+        const int64_t e = q * np + p;
+        const int64_t o = (int64_t)inv[e] * slotsK + s;
+        int gid = pi[o];
+        if (gid >= 0 && mode == 0) gid = row_ids[row_off[probe[e]] + gid];
+        cand[i] = gid >= 0 ? ivf_pack(pk[o], gid) : 0ull;
+    }
+    float qq = 0.f;
+    if (mode == 0) {
+        for (int c = lane; c < D; c += 64) { const float v = Q[q * D + c]; qq += v * v; }
+        qq = wave_sum(qq);
+    }
+    __syncthreads();
+    for (int j = 0; j < k_out; ++j) {
+        unsigned long long best = 0ull; int bi = -1;
+        for (int i = lane; i < M; i += 64)
+            if (cand[i] > best) { best = cand[i]; bi = i; }
+#pragma unroll
+        for (int s2 = 32; s2 > 0; s2 >>= 1) {
+            const unsigned long long ob = __shfl_xor(best, s2, 64);
+            const int oi = __shfl_xor(bi, s2, 64);
+            if (ob > best) { best = ob; bi = oi; }
+        }
+        if (lane == 0) {
+            if (best == 0ull) { out_ids[q * k_out + j] = -1; out_dist[q * k_out + j] = INFINITY; }
+            else {
+                const float key = ivf_unpack_key(best);
+                out_ids[q * k_out + j] = ivf_unpack_id(best);
+                out_dist[q * k_out + j] = mode == 0 ? fmaxf(qq - 2.f * key, 0.f) : -key;
+                cand[bi] = 0ull;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+static bool ivf_dim_ok(int dim) { return dim == 64 || dim == 128 || dim == 256; }
+static int ivf_nbits(int nb) { int b = 0; while ((1 << b) < nb) ++b; return b; }
+static int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
+
+// parts per list of a search: enough workgroups for the chip when few queries probe, within the merge's candidate budget
+static int ivf_parts(int64_t n_pairs, int np, int K, int kind) {
+    const int slots_per_part = kind == 0 ? 2 : 1;
+    const int64_t cap = std::max<int64_t>(1, IVF_MAX_CANDS / ((int64_t)np * slots_per_part * K));
+    const int64_t base = kind == 0 ? (n_pairs + 127) / 128 : n_pairs;
+    const int64_t want = base > 0 ? (2048 + base - 1) / base : 1;
+    return (int)std::max<int64_t>(1, std::min(cap, want));
+}
+
+struct IvfSearchLayout {
+    int np, K, parts, slotsK;
+    int64_t n_pairs, bucket_ws;
+    int64_t o_probe, o_pair_off, o_sorted, o_qmap, o_plist, o_inv, o_qblk, o_pk, o_pi, o_bucket, total;
+};
+
+}  // namespace nafp
+
+using namespace nafp;
+
+extern "C" int64_t nafp_ivf_bucket_workspace_bytes(int64_t n, int n_buckets, int batch) {
+    if (n < 0 || n >= ((int64_t)1 << 31) || n_buckets <= 0 || n_buckets > IVF_MAX_BUCKETS || batch <= 0) return -1;
+    const int64_t n_tiles = std::max<int64_t>(1, (n + BUCKET_TILE - 1) / BUCKET_TILE);
+    return align256((int64_t)batch * n_tiles * n_buckets * 4) + align256((int64_t)batch * n_buckets * 4) + 256;
+}
+
+extern "C" int nafp_ivf_bucket(const void* keys, int key_bytes, int64_t n, int n_buckets, int batch, int32_t* offsets, int32_t* ids,
+                               void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!keys || !offsets || !ids || !workspace || n < 0 || n_buckets <= 0 || batch <= 0) return NAFP_ERR_INVALID_ARG;
+    if ((key_bytes != 1 && key_bytes != 4) || n_buckets > IVF_MAX_BUCKETS || n >= ((int64_t)1 << 31)) return NAFP_ERR_UNSUPPORTED;
+    if (workspace_bytes < nafp_ivf_bucket_workspace_bytes(n, n_buckets, batch)) return NAFP_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int n_tiles = (int)std::max<int64_t>(1, (n + BUCKET_TILE - 1) / BUCKET_TILE);
+    char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    int* tc = (int*)ws;
+    int* totals = (int*)(ws + align256((int64_t)batch * n_tiles * n_buckets * 4));
+    const dim3 grid((unsigned)n_tiles, (unsigned)batch);
+    const int lds = n_buckets * 4, nbits = ivf_nbits(n_buckets);
+    if (key_bytes == 1) ivf_bucket_count_kernel<unsigned char><<<grid, 64, lds, st>>>((const unsigned char*)keys, n, n_buckets, batch, tc, n_tiles);
+    else                ivf_bucket_count_kernel<int><<<grid, 64, lds, st>>>((const int*)keys, n, n_buckets, batch, tc, n_tiles);
+    NAFP_LAUNCH_CHECK();
+    ivf_bucket_scan_tiles_kernel<<<dim3((unsigned)((n_buckets + 255) / 256), (unsigned)batch), 256, 0, st>>>(tc, n_tiles, n_buckets, totals);
+    NAFP_LAUNCH_CHECK();
+    ivf_bucket_offsets_kernel<<<(unsigned)batch, 256, 0, st>>>(totals, n_buckets, offsets);
+    NAFP_LAUNCH_CHECK();
+    if (key_bytes == 1) ivf_bucket_scatter_kernel<unsigned char><<<grid, 64, lds, st>>>((const unsigned char*)keys, n, n_buckets, batch, tc, offsets, ids, n_tiles, nbits);
+    else                ivf_bucket_scatter_kernel<int><<<grid, 64, lds, st>>>((const int*)keys, n, n_buckets, batch, tc, offsets, ids, n_tiles, nbits);
+    NAFP_LAUNCH_CHECK();
+    return NAFP_OK;
+}
+
+extern "C" int nafp_ivf_kmeans_update(const float* x, int64_t n, int dim, int batch, const int32_t* offsets, const int32_t* ids,
+                                      int n_buckets, float* centroids, int32_t* counts, void* stream) {
+    if (!x || !offsets || !ids || !centroids || !counts || n <= 0 || dim <= 0 || batch <= 0 || n_buckets <= 0) return NAFP_ERR_INVALID_ARG;
+    if (dim % batch || n_buckets > IVF_MAX_BUCKETS || n >= ((int64_t)1 << 31)) return NAFP_ERR_UNSUPPORTED;
+    ivf_kmeans_update_kernel<<<dim3((unsigned)n_buckets, (unsigned)batch), 64, 0, (hipStream_t)stream>>>(
+        x, n, dim, dim / batch, offsets, ids, n_buckets, centroids, counts);
+    NAFP_LAUNCH_CHECK();
+    return NAFP_OK;
+}
+
+extern "C" int nafp_ivf_residuals(const float* x, int64_t n, int dim, const int32_t* assign, const float* centroids, float* out,
+                                  void* stream) {
+    if (!x || !assign || !centroids || !out || n < 0) return NAFP_ERR_INVALID_ARG;
+    if (!ivf_dim_ok(dim)) return NAFP_ERR_UNSUPPORTED;
+    if (n == 0) return NAFP_OK;
+    ivf_residual_kernel<<<(unsigned)((n * dim + 255) / 256), 256, 0, (hipStream_t)stream>>>(x, n, dim, assign, centroids, out);
+    NAFP_LAUNCH_CHECK();
+    return NAFP_OK;
+}
+
+extern "C" int nafp_ivf_pq_encode(const float* x, int64_t n, int dim, const int32_t* assign, const float* coarse,
+                                  const float* pq_centroids, int M, uint8_t* codes, void* stream) {
+    if (!x || !pq_centroids || !codes || n < 0 || (!assign) != (!coarse)) return NAFP_ERR_INVALID_ARG;
+    if (!ivf_dim_ok(dim) || M != PQ_M || n >= ((int64_t)1 << 31)) return NAFP_ERR_UNSUPPORTED;
+    if (n == 0) return NAFP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int dsub = dim / M;
+    const dim3 grid((unsigned)((n + 255) / 256), (unsigned)dsub);          // 64 / dsub sub-spaces per workgroup
+    if (dsub == 1)      ivf_pq_encode_kernel<1><<<grid, 256, 0, st>>>(x, n, assign, coarse, pq_centroids, codes);
+    else if (dsub == 2) ivf_pq_encode_kernel<2><<<grid, 256, 0, st>>>(x, n, assign, coarse, pq_centroids, codes);
+    else                ivf_pq_encode_kernel<4><<<grid, 256, 0, st>>>(x, n, assign, coarse, pq_centroids, codes);
+    NAFP_LAUNCH_CHECK();
+    return NAFP_OK;
+}
+
+extern "C" int nafp_ivf_probe(const float* query, int64_t n_query, const float* centroids, int nlist, int dim, int nprobe,
+                              int32_t* probe, void* stream) {
+    if (!query || !centroids || !probe || n_query < 0 || nlist <= 0 || nprobe <= 0) return NAFP_ERR_INVALID_ARG;
+    if (!ivf_dim_ok(dim) || nprobe > 128 || nprobe > nlist || nlist > IVF_MAX_BUCKETS || n_query > (1 << 30)) return NAFP_ERR_UNSUPPORTED;
+    if (n_query == 0) return NAFP_OK;
+    const int lds = (dim + nlist) * 4;
+    NAFP_HIP_CHECK(hipFuncSetAttribute((const void*)ivf_probe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    ivf_probe_kernel<<<(unsigned)n_query, 256, lds, (hipStream_t)stream>>>(query, centroids, nlist, dim, nprobe, probe);
+    NAFP_LAUNCH_CHECK();
+    return NAFP_OK;
+}
+
+extern "C" int64_t nafp_ivf_flat_rows_bound(int64_t n, int nlist) {
+    if (n < 0 || nlist <= 0) return -1;
+    return n + 63ll * nlist;
+}
+
+extern "C" int nafp_ivf_flat_lists(const float* x, int64_t n, int dim, const int32_t* offsets, const int32_t* ids, int nlist,
+                                   int32_t* row_offsets, float* rows, float* half_norms, int32_t* row_ids, void* stream) {
+    if (!x || !offsets || !ids || !row_offsets || !rows || !half_norms || !row_ids || n <= 0 || nlist <= 0) return NAFP_ERR_INVALID_ARG;
+    if (!ivf_dim_ok(dim) || nlist > IVF_MAX_BUCKETS || nafp_ivf_flat_rows_bound(n, nlist) >= ((int64_t)1 << 31)) return NAFP_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    ivf_padded_offsets_kernel<<<1, 64, 0, st>>>(offsets, nlist, row_offsets);
+    NAFP_LAUNCH_CHECK();
+    const int64_t bound = nafp_ivf_flat_rows_bound(n, nlist);
+    ivf_flat_lists_kernel<<<(unsigned)((bound + 255) / 256), 256, 0, st>>>(x, dim, offsets, ids, nlist, row_offsets, bound, rows,
+                                                                           half_norms, row_ids);
+    NAFP_LAUNCH_CHECK();
+    return NAFP_OK;
+}
+
+extern "C" int nafp_ivf_pq_lists(const uint8_t* codes, int64_t n, int M, const int32_t* ids, uint8_t* codes_sorted, void* stream) {
+    if (!codes || !ids || !codes_sorted || n < 0) return NAFP_ERR_INVALID_ARG;
+    if (M != PQ_M || n >= ((int64_t)1 << 31)) return NAFP_ERR_UNSUPPORTED;
+    if (n == 0) return NAFP_OK;
+    ivf_gather_codes_kernel<<<(unsigned)((n * 4 + 255) / 256), 256, 0, (hipStream_t)stream>>>((const uint4*)codes, ids, n, (uint4*)codes_sorted);
+    NAFP_LAUNCH_CHECK();
+    return NAFP_OK;
+}
+
+static bool ivf_search_layout(int64_t n_query, int nlist, int nprobe, int k, int kind, IvfSearchLayout* L) {
+    if (n_query < 0 || n_query > (1 << 30) || nlist <= 0 || nlist > IVF_MAX_BUCKETS || nprobe <= 0 || nprobe > 128 || k <= 0 ||
+        k > 32 || (kind != 0 && kind != 1))
+        return false;
+    L->np = std::min(nprobe, nlist);
+    L->K = k <= 20 ? 20 : 32;
+    L->n_pairs = n_query * L->np;
+    if (L->n_pairs >= ((int64_t)1 << 31)) return false;
+    L->parts = ivf_parts(L->n_pairs, L->np, L->K, kind);
+    L->slotsK = (kind == 0 ? 2 : 1) * L->parts * L->K;
+    L->bucket_ws = nafp_ivf_bucket_workspace_bytes(L->n_pairs, nlist, 1);
+    int64_t at = 0;
+    auto take = [&](int64_t bytes) { const int64_t o = at; at += align256(bytes); return o; };
+    L->o_probe = take(L->n_pairs * 4);
+    L->o_pair_off = take((int64_t)(nlist + 1) * 4);
+    L->o_sorted = take(L->n_pairs * 4);
+    L->o_qmap = take(L->n_pairs * 4);
+    L->o_plist = take(L->n_pairs * 4);
+    L->o_inv = take(L->n_pairs * 4);
+    L->o_qblk = take((int64_t)(nlist + 1) * 4);
+    L->o_pk = take(L->n_pairs * L->slotsK * 4);
+    L->o_pi = take(L->n_pairs * L->slotsK * 4);
+    L->o_bucket = take(L->bucket_ws);
+    L->total = at + 256;
+    return true;
+}
+
+extern "C" int64_t nafp_ivf_search_workspace_bytes(int64_t n_query, int nlist, int nprobe, int k, int kind) {
+    IvfSearchLayout L;
+    return ivf_search_layout(n_query, nlist, nprobe, k, kind, &L) ? L.total : -1;
+}
+
+// probe, group the (query, probe) pairs by list; returns the workspace base
+static int ivf_search_front(const float* query, int64_t n_query, const float* centroids, int nlist, int dim, const IvfSearchLayout& L,
+                            char* ws, hipStream_t st) {
+    int rc = nafp_ivf_probe(query, n_query, centroids, nlist, dim, L.np, (int*)(ws + L.o_probe), st);
+    if (rc != NAFP_OK) return rc;
+    rc = nafp_ivf_bucket(ws + L.o_probe, 4, L.n_pairs, nlist, 1, (int*)(ws + L.o_pair_off), (int*)(ws + L.o_sorted), ws + L.o_bucket,
+                         L.bucket_ws, st);
+    if (rc != NAFP_OK) return rc;
+    ivf_pairs_kernel<<<(unsigned)((L.n_pairs + 255) / 256), 256, 0, st>>>((const int*)(ws + L.o_sorted), (const int*)(ws + L.o_probe),
+                                                                          L.n_pairs, L.np, (int*)(ws + L.o_qmap), (int*)(ws + L.o_plist),
+                                                                          (int*)(ws + L.o_inv));
+    NAFP_LAUNCH_CHECK();
+    return NAFP_OK;
+}
+
+static int ivf_search_merge(const IvfSearchLayout& L, char* ws, int64_t n_query, const int32_t* row_ids, const int32_t* row_off,
+                            const float* query, int dim, int mode, float* out_dist, int32_t* out_ids, int k, hipStream_t st) {
+    const int lds = L.np * L.slotsK * 8;
+    NAFP_HIP_CHECK(hipFuncSetAttribute((const void*)ivf_merge_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    ivf_merge_kernel<<<(unsigned)n_query, 64, lds, st>>>((const float*)(ws + L.o_pk), (const int*)(ws + L.o_pi), (const int*)(ws + L.o_inv),
+                                                         (const int*)(ws + L.o_probe), L.np, L.slotsK, row_ids, row_off, query, dim, mode,
+                                                         out_dist, out_ids, k);
+    NAFP_LAUNCH_CHECK();
+    return NAFP_OK;
+}
+
+extern "C" int nafp_ivf_flat_search(const float* query, int64_t n_query, const float* centroids, int nlist, int dim, int nprobe,
+                                    const float* rows, const float* half_norms, const int32_t* row_offsets, const int32_t* row_ids,
+                                    int k, float* out_dist, int32_t* out_ids, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!query || !centroids || !rows || !half_norms || !row_offsets || !row_ids || !out_dist || !out_ids || !workspace || n_query < 0 ||
+        nlist <= 0 || nprobe <= 0 || k <= 0)
+        return NAFP_ERR_INVALID_ARG;
+    IvfSearchLayout L;
+    if (!ivf_dim_ok(dim) || !ivf_search_layout(n_query, nlist, nprobe, k, 0, &L)) return NAFP_ERR_UNSUPPORTED;
+    if (n_query == 0) return NAFP_OK;
+    if (workspace_bytes < L.total) return NAFP_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    int rc = ivf_search_front(query, n_query, centroids, nlist, dim, L, ws, st);
+    if (rc != NAFP_OK) return rc;
+    ivf_qblock_prefix_kernel<<<1, 64, 0, st>>>((const int*)(ws + L.o_pair_off), nlist, (int*)(ws + L.o_qblk));
+    NAFP_LAUNCH_CHECK();
+    const unsigned grid_x = (unsigned)((L.n_pairs + 127) / 128 + nlist);        // >= the number of (list, query block) tasks
+    rc = ivf_flat_scan_launch(dim, L.K, grid_x, L.parts, query, (const int*)(ws + L.o_qmap), (const int*)(ws + L.o_pair_off),
+                              (const int*)(ws + L.o_qblk), nlist, rows, half_norms, row_offsets, (float*)(ws + L.o_pk),
+                              (int*)(ws + L.o_pi), st);
+    if (rc != NAFP_OK) return rc;
+    return ivf_search_merge(L, ws, n_query, row_ids, row_offsets, query, dim, 0, out_dist, out_ids, k, st);
+}
+
+extern "C" int nafp_ivf_pq_search(const float* query, int64_t n_query, const float* centroids, int nlist, int dim, int nprobe,
+                                  const float* pq_centroids, int M, const uint8_t* codes_sorted, const int32_t* offsets,
+                                  const int32_t* ids, int k, float* out_dist, int32_t* out_ids, void* workspace, int64_t workspace_bytes,
+                                  void* stream) {
+    if (!query || !centroids || !pq_centroids || !codes_sorted || !offsets || !ids || !out_dist || !out_ids || !workspace ||
+        n_query < 0 || nlist <= 0 || nprobe <= 0 || k <= 0)
+        return NAFP_ERR_INVALID_ARG;
+    IvfSearchLayout L;
+    if (!ivf_dim_ok(dim) || M != PQ_M || !ivf_search_layout(n_query, nlist, nprobe, k, 1, &L)) return NAFP_ERR_UNSUPPORTED;
+    if (n_query == 0) return NAFP_OK;
+    if (workspace_bytes < L.total) return NAFP_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    int rc = ivf_search_front(query, n_query, centroids, nlist, dim, L, ws, st);
+    if (rc != NAFP_OK) return rc;
+    const int lds = (PQ_M * PQ_KS + 256) * 4 + 4 * 8;
+    const dim3 grid((unsigned)L.n_pairs, (unsigned)L.parts);
+    const int* qm = (const int*)(ws + L.o_qmap);
+    const int* pl = (const int*)(ws + L.o_plist);
+    float* pk = (float*)(ws + L.o_pk);
+    int* pi = (int*)(ws + L.o_pi);
+#define NAFP_PQ_SCAN(DS_, K_)                                                                                                   \
+    {                                                                                                                           \
+        NAFP_HIP_CHECK(hipFuncSetAttribute((const void*)ivf_pq_scan_kernel<DS_, K_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); \
+        ivf_pq_scan_kernel<DS_, K_><<<grid, 256, lds, st>>>(query, qm, pl, centroids, pq_centroids, codes_sorted, offsets, ids,    \
+                                                            L.parts, pk, pi);                                                    \
+    }
+    const int dsub = dim / PQ_M;
+    if (L.K == 20) { if (dsub == 1) NAFP_PQ_SCAN(1, 20) else if (dsub == 2) NAFP_PQ_SCAN(2, 20) else NAFP_PQ_SCAN(4, 20) }
+    else           { if (dsub == 1) NAFP_PQ_SCAN(1, 32) else if (dsub == 2) NAFP_PQ_SCAN(2, 32) else NAFP_PQ_SCAN(4, 32) }
+#undef NAFP_PQ_SCAN
+    NAFP_LAUNCH_CHECK();
+    return ivf_search_merge(L, ws, n_query, nullptr, nullptr, query, dim, 1, out_dist, out_ids, k, st);
+}

@@ -16,6 +16,7 @@
 //                              as a sorted register list (threshold test per score, unrolled insertion
 //                              only when a score beats the K-th best).  blockIdx.y splits the index.
 //   search_merge_kernel<K>     merges the 2 x splits partial lists of a query (key desc, id asc)
+//   ivf_flat_scan_kernel<D,K>  the same body over one inverted list's rows for the queries that probe it (ivf.hip)
 //   search_seq_score_kernel<D> mean_i q[t+i] . x[c+i] for candidate sequence starts c (eval_faiss.py:221-230)
 #include "nafp_common.h"
 
@@ -58,7 +59,10 @@ constexpr int TILE_ROWS = 64;
 template <int D, int K>
 __device__ __forceinline__ void search_topk_body(
         const float* __restrict__ Q, const float* __restrict__ X, const float* __restrict__ hn,
-        float* __restrict__ out_key, int* __restrict__ out_id, int nq, int64_t N, int tiles_per_split, int n_lists) {
+        float* __restrict__ out_key, int* __restrict__ out_id, int nq, int64_t N, int tiles_per_split, int n_lists,
+        int qb, int split, const int* __restrict__ qmap) {
+    // qb / split: the query block and index split of this workgroup (blockIdx.x / .y for the exact search); qmap: the row of
+    // Q that query qn of the block reads (nullptr: row qn; the IVF scan reads its list's queries through it, ivf.hip)
     constexpr int CH = D / 4;                        // 16-B chunks per row
     constexpr int SWZ = (CH < 32 ? CH : 32) - 1;      // chunk swizzle mask: the row's low bits -- the same for row rl and row 32 + rl, which share `aoff` (d = 256 has 64 chunks)
     constexpr int RPI = 64 / CH;                     // rows per DMA wave-instruction
@@ -69,16 +73,16 @@ __device__ __forceinline__ void search_topk_body(
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int rl = lane & 31, hh = lane >> 5;
-    const int qn = blockIdx.x * 128 + wave * 32 + rl;
+    const int qn = qb * 128 + wave * 32 + rl;
     const int64_t n_tiles = (N + TILE_ROWS - 1) / TILE_ROWS;
-    const int64_t t0 = (int64_t)blockIdx.y * tiles_per_split;
+    const int64_t t0 = (int64_t)split * tiles_per_split;
     const int64_t t1 = std::min<int64_t>(n_tiles, t0 + tiles_per_split);
 
     // the query column of this lane: q[8kk + 4hh + j], j = 0..3 (the k permutation A uses too)
     float4 qr[D / 8];
 #pragma unroll
     for (int kk = 0; kk < D / 8; ++kk)
-        qr[kk] = qn < nq ? *(const float4*)(Q + (int64_t)qn * D + 8 * kk + 4 * hh) : make_float4(0.f, 0.f, 0.f, 0.f);
+        qr[kk] = qn < nq ? *(const float4*)(Q + (int64_t)(qmap ? qmap[qn] : qn) * D + 8 * kk + 4 * hh) : make_float4(0.f, 0.f, 0.f, 0.f);
 
     float sc[K]; int id[K];
 #pragma unroll
@@ -166,7 +170,7 @@ __device__ __forceinline__ void search_topk_body(
 #undef NAFP_S_TILE
 #undef NAFP_S_DMA
     if (qn < nq) {
-        const int64_t o = ((int64_t)qn * n_lists + blockIdx.y * 2 + hh) * K;
+        const int64_t o = ((int64_t)qn * n_lists + split * 2 + hh) * K;
 #pragma unroll
         for (int j = 0; j < K; ++j) { out_key[o + j] = sc[j]; out_id[o + j] = id[j]; }
     }
@@ -176,7 +180,7 @@ template <int D, int K>
 __global__ __launch_bounds__(256, 2) void search_topk_kernel(
         const float* __restrict__ Q, const float* __restrict__ X, const float* __restrict__ hn,
         float* __restrict__ out_key, int* __restrict__ out_id, int nq, int64_t N, int tiles_per_split, int n_lists) {
-    search_topk_body<D, K>(Q, X, hn, out_key, out_id, nq, N, tiles_per_split, n_lists);
+    search_topk_body<D, K>(Q, X, hn, out_key, out_id, nq, N, tiles_per_split, n_lists, blockIdx.x, blockIdx.y, nullptr);
 }
 // d = 256 (EMB_SZ 256: the encoder and NT-Xent support it, so the exact index does too): a lane keeps 128 floats of its query
 // column, and the 2-tile ring is 128 KB of LDS -- one workgroup per CU either way, so the kernel may use the whole register file
@@ -184,7 +188,68 @@ template <int K>
 __global__ __launch_bounds__(256, 1) void search_topk_kernel_d256(
         const float* __restrict__ Q, const float* __restrict__ X, const float* __restrict__ hn,
         float* __restrict__ out_key, int* __restrict__ out_id, int nq, int64_t N, int tiles_per_split, int n_lists) {
-    search_topk_body<256, K>(Q, X, hn, out_key, out_id, nq, N, tiles_per_split, n_lists);
+    search_topk_body<256, K>(Q, X, hn, out_key, out_id, nq, N, tiles_per_split, n_lists, blockIdx.x, blockIdx.y, nullptr);
+}
+
+// IVF-Flat scan (ivf.hip, nafp_ivf_flat_search): the body above over ONE inverted list's rows (padded to whole tiles, +inf half
+// norms in the padding) with a 128-query block of the (query, probe) pairs that probe that list as the query block.  Task x
+// (blockIdx.x) = (list l, query block qb) found in the prefix of per-list query blocks; blockIdx.y = one of `parts` row splits.
+// Ids written are rows relative to the list's first row; the merge maps them back through the list's id array.
+template <int D, int K>
+__device__ __forceinline__ void ivf_flat_scan_body(const float* __restrict__ Q, const int* __restrict__ qmap,
+                                                   const int* __restrict__ pair_off, const int* __restrict__ qblk_off, int nlist,
+                                                   const float* __restrict__ Xs, const float* __restrict__ hns,
+                                                   const int* __restrict__ row_off, float* __restrict__ pk, int* __restrict__ pi,
+                                                   int parts) {
+    const int task = blockIdx.x;
+    if (task >= qblk_off[nlist]) return;                          // the grid is an upper bound of the task count
+    int lo = 0, hi = nlist;                                       // the largest l with qblk_off[l] <= task
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (qblk_off[mid] <= task) lo = mid; else hi = mid; }
+    const int p0 = pair_off[lo], r0 = row_off[lo];
+    const int64_t N = row_off[lo + 1] - r0;
+    const int64_t n_tiles = N / TILE_ROWS;
+    const int tps = (int)((n_tiles + parts - 1) / parts);
+    search_topk_body<D, K>(Q, Xs + (int64_t)r0 * D, hns + r0, pk + (int64_t)p0 * 2 * parts * K, pi + (int64_t)p0 * 2 * parts * K,
+                           pair_off[lo + 1] - p0, N, tps, 2 * parts, task - qblk_off[lo], blockIdx.y, qmap + p0);
+}
+template <int D, int K>
+__global__ __launch_bounds__(256, 2) void ivf_flat_scan_kernel(const float* __restrict__ Q, const int* __restrict__ qmap,
+        const int* __restrict__ pair_off, const int* __restrict__ qblk_off, int nlist, const float* __restrict__ Xs,
+        const float* __restrict__ hns, const int* __restrict__ row_off, float* __restrict__ pk, int* __restrict__ pi, int parts) {
+    ivf_flat_scan_body<D, K>(Q, qmap, pair_off, qblk_off, nlist, Xs, hns, row_off, pk, pi, parts);
+}
+template <int K>
+__global__ __launch_bounds__(256, 1) void ivf_flat_scan_kernel_d256(const float* __restrict__ Q, const int* __restrict__ qmap,
+        const int* __restrict__ pair_off, const int* __restrict__ qblk_off, int nlist, const float* __restrict__ Xs,
+        const float* __restrict__ hns, const int* __restrict__ row_off, float* __restrict__ pk, int* __restrict__ pi, int parts) {
+    ivf_flat_scan_body<256, K>(Q, qmap, pair_off, qblk_off, nlist, Xs, hns, row_off, pk, pi, parts);
+}
+
+template <int D, int K>
+static int launch_ivf_flat(unsigned grid_x, int parts, const float* Q, const int* qmap, const int* pair_off, const int* qblk_off,
+                           int nlist, const float* Xs, const float* hns, const int* row_off, float* pk, int* pi, hipStream_t st) {
+    const int lds = 2 * TILE_ROWS * D * (int)sizeof(float);
+    const dim3 grid(grid_x, (unsigned)parts);
+    if constexpr (D == 256) {
+        NAFP_HIP_CHECK(hipFuncSetAttribute((const void*)ivf_flat_scan_kernel_d256<K>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        ivf_flat_scan_kernel_d256<K><<<grid, 256, lds, st>>>(Q, qmap, pair_off, qblk_off, nlist, Xs, hns, row_off, pk, pi, parts);
+    } else {
+        NAFP_HIP_CHECK(hipFuncSetAttribute((const void*)ivf_flat_scan_kernel<D, K>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        ivf_flat_scan_kernel<D, K><<<grid, 256, lds, st>>>(Q, qmap, pair_off, qblk_off, nlist, Xs, hns, row_off, pk, pi, parts);
+    }
+    NAFP_LAUNCH_CHECK();
+    return NAFP_OK;
+}
+
+// host entry for ivf.hip (same library): K is 20 or 32, D 64 / 128 / 256
+int ivf_flat_scan_launch(int D, int K, unsigned grid_x, int parts, const float* Q, const int* qmap, const int* pair_off,
+                         const int* qblk_off, int nlist, const float* Xs, const float* hns, const int* row_off, float* pk, int* pi,
+                         hipStream_t st) {
+#define NAFP_IVF_L(D_, K_) launch_ivf_flat<D_, K_>(grid_x, parts, Q, qmap, pair_off, qblk_off, nlist, Xs, hns, row_off, pk, pi, st)
+    if (D == 128) return K == 20 ? NAFP_IVF_L(128, 20) : NAFP_IVF_L(128, 32);
+    if (D == 256) return K == 20 ? NAFP_IVF_L(256, 20) : NAFP_IVF_L(256, 32);
+    return K == 20 ? NAFP_IVF_L(64, 20) : NAFP_IVF_L(64, 32);
+#undef NAFP_IVF_L
 }
 
 __device__ __forceinline__ unsigned long long pack_key(float key, int id) {

@@ -3,7 +3,9 @@
 Host mirror of the reference's eval/eval_faiss.py (`load_memmap_data` :18-62, `eval_faiss` :93-275)
 and of `get_index` (eval/utils/get_index_faiss.py:10-121) for index_type 'L2' -- the exact
 faiss.IndexFlatL2 -- backed by libnafp's search kernels (include/nafp.h "Search / evaluation").
-The approximate index types (IVF, IVFPQ, IVFPQ-RR, IVFPQ-ONDISK, HNSW) are not built: a request for one of them
+With NAFP_APPROX_INDEX=1 in the environment, 'ivf' and 'ivfpq' build real IVF-Flat / IVF-PQ indexes on the device (eval/ivf.py,
+opt-in; `index_used.json` then names the index and its parameters).  Otherwise, and always for IVFPQ-RR, IVFPQ-ONDISK and HNSW,
+the approximate index types are not built: a request for one of them
 (the reference's default is `-i ivfpq`) is SERVED BY THE EXACT SEARCH, with a notice on stderr and the substitution
 recorded in `index_used.json` next to `raw_score.npy` -- on an MI355X the whole [dummy_db ; db] table stays resident
 in HBM (51 GB for 100 M fingerprints out of 288 GB), and the exact index is the accuracy ceiling of the approximate ones.
@@ -128,13 +130,35 @@ class FlatL2Index:
         return out
 
 
+# NAFP_APPROX_INDEX=1: 'ivf' and 'ivfpq' build real approximate indexes (eval/ivf.py) with the reference's parameters
+# (get_index_faiss.py:64-74, nprobe = 40 at :120) instead of being served by the exact search.
+APPROX_INDEX_PARAMS = {'ivf': dict(nlist=400, nprobe=40), 'ivfpq': dict(nlist=256, M=64, nbits=8, nprobe=40)}
+
+
+def approx_index_enabled():
+    return os.environ.get('NAFP_APPROX_INDEX', '') == '1'
+
+
 def get_index(index_type, train_data, train_data_shape, use_gpu=True, max_nitem_train=2e7):
-    """get_index_faiss.py:10-121 for the exact index."""
+    """get_index_faiss.py:10-121 for the exact index (and, opted in, IVF / IVFPQ)."""
     mode = index_type.lower()
     if mode == 'l2':
         if not use_gpu:
             raise NotImplementedError('--nogpu: this build has no CPU search path')
         return FlatL2Index(int(train_data_shape[1]))
+    if mode in APPROX_INDEX_PARAMS and approx_index_enabled():
+        if not use_gpu:
+            raise NotImplementedError('--nogpu: this build has no CPU search path')
+        from .ivf import IVFFlatIndex, IVFPQIndex, training_subset
+        p = APPROX_INDEX_PARAMS[mode]
+        d = int(train_data_shape[1])
+        index = IVFFlatIndex(d, p['nlist']) if mode == 'ivf' else IVFPQIndex(d, p['nlist'], p['M'], p['nbits'])
+        index.nprobe = p['nprobe']
+        start_time = time.time()
+        index.train(training_subset(train_data, max_nitem_train, index.seed))
+        print(f'Trained {index.index_description} in {time.time() - start_time:.2f} sec.')
+        index.requested_type = index_type
+        return index
     if mode in ('ivf', 'ivfpq', 'ivfpq-rr', 'ivfpq-ondisk', 'hnsw'):
         # get_index_faiss.py:64-121 builds an approximate faiss index here (run.py:118 default 'ivfpq').  None of them is
         # built; the exact search over the HBM-resident table is the accuracy ceiling of every one of them, so the request
@@ -256,6 +280,13 @@ def eval_faiss(emb_dir, emb_dummy_dir=None, index_type='l2', nogpu=False, max_tr
     # search the numbers are not comparable with the reference's IVF-PQ figures: say so NEXT TO them
     import json
     requested = getattr(index, 'requested_type', index_type)
+    if hasattr(index, 'index_description'):                     # an approximate index really served the run (opted in)
+        with open(f'{emb_dir}/index_used.json', 'w') as f:
+            json.dump({'index_type_requested': requested, 'index_type_used': index.index_description, 'substituted': False,
+                       'k_probe': int(k_probe), 'note': 'hit rates in raw_score.npy are those of the approximate index '
+                                                        '(NAFP_APPROX_INDEX=1)'}, f, indent=1)
+        print(f'Saved test_ids and raw score to {emb_dir}.')
+        return rates
     with open(f'{emb_dir}/index_used.json', 'w') as f:
         json.dump({'index_type_requested': requested, 'index_type_used': 'L2 (exact, HIP FlatL2Index)',
                    'substituted': requested.lower() != 'l2', 'k_probe': int(k_probe),

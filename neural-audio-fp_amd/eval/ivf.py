@@ -1,0 +1,400 @@
+"""IVF-Flat and IVF-PQ indexes on the device: faiss.IndexIVFFlat / faiss.IndexIVFPQ as the reference builds them for
+evaluation (eval/utils/get_index_faiss.py:64-80, nprobe = 40 at :120), backed by libnafp's IVF kernels (include/nafp.h
+"Approximate indexes", csrc/ivf.hip).  Opt-in from `get_index` (NAFP_APPROX_INDEX=1, eval_faiss.py).
+
+faiss-shaped surface: `train(x)`, `is_trained`, `add(x)` (repeatedly), `ntotal`, a settable `nprobe`, `search(q, k)` ->
+(D, I) numpy, `search_device`; plus what the evaluation needs (`device`, `sequence_scores`, `reconstruct_n`: the original fp32
+rows in insertion order, kept in a FlatL2Index -- the reference's `fake_recon_index`) and, for tests and re-use, `centroids`,
+`pq_centroids`, `probe_device(q)` and `set_params(...)` / explicit k-means initialisations in `train`.
+
+Training is modelled on faiss's CPU defaults (documentation and source as publicly known; faiss is not a dependency, so this is
+the project's contract rather than a checked copy).  Every constant of it is below.  torch only allocates and copies here; the
+k-means empty-cluster split is tiny and sequential and runs on the host (numpy).
+"""
+import numpy as np
+import torch
+
+from .. import _lib
+
+DEFAULT_SEED = 1234
+MAX_POINTS_PER_CENTROID = 256            # k-means training points per centroid (seeded subset beyond)
+COARSE_ITERS = 10
+PQ_ITERS = 25
+PQ_MAX_TRAIN = 1024 * 256                # training points of the PQ stage (seeded subset beyond)
+PQ_KS = 256                              # nbits = 8
+SPLIT_EPS = 1.0 / 1024                   # empty-cluster split: the two copies are scaled by 1 +- SPLIT_EPS
+MAX_NPROBE = 128
+MAX_K = 32
+MAX_NLIST = 16384
+ASSIGN_CHUNK = 1 << 20                   # rows per coarse-assignment launch (the exact kernel's workspace grows with them)
+
+# independent random streams of one seed
+STREAM_TRAIN_SUBSET, STREAM_COARSE, STREAM_COARSE_SPLIT, STREAM_PQ, STREAM_PQ_SPLIT = range(5)
+
+
+def rng_for(seed, stream):
+    return np.random.default_rng([int(seed), int(stream)])
+
+
+def subset_indices(n, n_max, rng):
+    """Sorted indices of a seeded random subset of n_max of n rows (all rows if n <= n_max)."""
+    if n <= n_max:
+        return None
+    return np.sort(rng.permutation(n)[:int(n_max)])
+
+
+def training_subset(x, n_max, seed=DEFAULT_SEED):
+    """get_index's training set: x, or a seeded random subset of int(n_max) of its rows (the reference draws it unseeded)."""
+    idx = subset_indices(len(x), int(n_max), rng_for(seed, STREAM_TRAIN_SUBSET))
+    return x if idx is None else _take(x, idx)
+
+
+def _take(x, idx):
+    if torch.is_tensor(x):
+        return x[torch.from_numpy(idx).to(x.device)]
+    return np.asarray(x[idx], dtype=np.float32)
+
+
+def split_empty_clusters(cent, counts, rng):
+    """faiss's split of empty clusters, in place on cent (k, dsub) / counts (k,): for each empty cluster in order, a donor is
+    drawn with probability proportional to (size - 1) (one uniform draw against the cumulative weights), its centroid copied
+    into the empty one, the two scaled by 1 +- SPLIT_EPS with the sign alternating per dimension, and its count halved."""
+    k, dsub = cent.shape
+    sign = np.where(np.arange(dsub) % 2 == 0, 1.0, -1.0)
+    up = (1.0 + sign * SPLIT_EPS).astype(cent.dtype)
+    down = (1.0 - sign * SPLIT_EPS).astype(cent.dtype)
+    for ci in range(k):
+        if counts[ci] != 0:
+            continue
+        w = np.maximum(counts.astype(np.float64) - 1.0, 0.0)
+        cum = np.cumsum(w)
+        cj = min(int(np.searchsorted(cum, rng.random() * cum[-1], side='right')), k - 1)
+        cent[ci] = cent[cj] * up
+        cent[cj] = cent[cj] * down
+        counts[ci] = counts[cj] // 2
+        counts[cj] -= counts[ci]
+    return cent, counts
+
+
+class _Dev:
+    """Thin wrappers of the C ABI on one device."""
+
+    def __init__(self, device):
+        self.device = device
+        self.lib = _lib.load()
+
+    def empty(self, shape, dtype):
+        return torch.empty(shape, dtype=dtype, device=self.device)
+
+    def bucket(self, keys, key_bytes, n, nb, batch=1):
+        lib = self.lib
+        offsets = self.empty((batch, nb + 1), torch.int32)
+        ids = self.empty((batch, max(n, 1)), torch.int32)
+        need = int(lib.nafp_ivf_bucket_workspace_bytes(n, nb, batch))
+        ws = self.empty((need,), torch.uint8)
+        _lib.check(lib.nafp_ivf_bucket(_lib.ptr(keys), key_bytes, n, nb, batch, _lib.ptr(offsets), _lib.ptr(ids), _lib.ptr(ws), need,
+                                       _lib.current_stream()), 'ivf_bucket')
+        return offsets, ids
+
+    def assign(self, x, cent, out=None):
+        """Nearest centroid per row (the exact search with k = 1 against the centroid table), in chunks."""
+        lib = self.lib
+        n, d = x.shape
+        nlist = cent.shape[0]
+        aux = self.empty((int(lib.nafp_search_index_aux_floats(nlist)),), torch.float32)
+        _lib.check(lib.nafp_search_index_prepare(_lib.ptr(cent), nlist, d, _lib.ptr(aux), _lib.current_stream()), 'search_index_prepare')
+        out = self.empty((n,), torch.int32) if out is None else out
+        dist = self.empty((min(n, ASSIGN_CHUNK),), torch.float32)
+        ws = None
+        for a in range(0, n, ASSIGN_CHUNK):
+            b = min(n, a + ASSIGN_CHUNK)
+            need = int(lib.nafp_search_workspace_bytes(b - a, nlist, 1))
+            if ws is None or ws.numel() < need:
+                ws = self.empty((need,), torch.uint8)
+            _lib.check(lib.nafp_search_topk_l2(_lib.ptr(x[a:b]), b - a, _lib.ptr(cent), _lib.ptr(aux), nlist, d, 1, _lib.ptr(dist),
+                                               _lib.ptr(out[a:b]), _lib.ptr(ws), ws.numel(), _lib.current_stream()), 'search_topk_l2')
+        return out
+
+    def pq_encode(self, x, cent_assign, coarse, pq, out=None):
+        n, d = x.shape
+        out = self.empty((n, pq.shape[0]), torch.uint8) if out is None else out
+        _lib.check(self.lib.nafp_ivf_pq_encode(_lib.ptr(x), n, d, _lib.ptr(cent_assign), _lib.ptr(coarse), _lib.ptr(pq), pq.shape[0],
+                                               _lib.ptr(out), _lib.current_stream()), 'ivf_pq_encode')
+        return out
+
+    def residuals(self, x, assign, cent):
+        out = torch.empty_like(x)
+        _lib.check(self.lib.nafp_ivf_residuals(_lib.ptr(x), x.shape[0], x.shape[1], _lib.ptr(assign), _lib.ptr(cent), _lib.ptr(out),
+                                               _lib.current_stream()), 'ivf_residuals')
+        return out
+
+    def kmeans(self, x, cent, nb, batch, niter, rng, assign_fn):
+        """Lloyd iterations on the device from the initial centroids `cent` (batch, nb, dsub), updated in place: assign (ties:
+        smaller id), bucket, mean in id order, host split of empty clusters.  Returns the final cluster sizes (batch, nb)."""
+        n, dim = x.shape
+        dsub = dim // batch
+        counts = self.empty((batch, nb), torch.int32)
+        c = None
+        for _ in range(niter):
+            keys, key_bytes = assign_fn(cent)
+            offsets, ids = self.bucket(keys, key_bytes, n, nb, batch)
+            _lib.check(self.lib.nafp_ivf_kmeans_update(_lib.ptr(x), n, dim, batch, _lib.ptr(offsets), _lib.ptr(ids), nb, _lib.ptr(cent),
+                                                       _lib.ptr(counts), _lib.current_stream()), 'ivf_kmeans_update')
+            c = counts.cpu().numpy().astype(np.int64)
+            if (c == 0).any():
+                h = cent.cpu().numpy().reshape(batch, nb, dsub)
+                for b in range(batch):
+                    split_empty_clusters(h[b], c[b], rng)
+                cent.copy_(torch.from_numpy(h).reshape(cent.shape))
+        return c
+
+
+def _as_device(x, device):
+    if torch.is_tensor(x):
+        return _lib.require_cuda(x, 'x').to(device=device, dtype=torch.float32).contiguous()
+    return torch.from_numpy(np.array(x, dtype=np.float32)).to(device)
+
+
+def kmeans(x, init, niter=COARSE_ITERS, seed=DEFAULT_SEED, device=None):
+    """k-means on the device from an explicit initialisation init (k, d): the coarse quantizer's training loop.
+    Returns (centroids (k, d) float32 numpy, final cluster sizes (k,))."""
+    dev = _Dev(torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device()))
+    xd = _as_device(x, dev.device)
+    cent = _as_device(init, dev.device).clone()
+    k = cent.shape[0]
+    counts = dev.kmeans(xd, cent, k, 1, niter, rng_for(seed, STREAM_COARSE_SPLIT), lambda c: (dev.assign(xd, c), 4))
+    return cent.cpu().numpy(), counts[0]
+
+
+class _IVFBase:
+    kind = None
+
+    def __init__(self, d, nlist, seed=DEFAULT_SEED, device=None):
+        from .eval_faiss import FlatL2Index
+        if d not in (64, 128, 256):
+            raise NotImplementedError(f'fingerprint dimension {d}')
+        if not 1 <= int(nlist) <= MAX_NLIST:
+            raise NotImplementedError(f'nlist = {nlist} (1 .. {MAX_NLIST})')
+        self.d, self.nlist, self.seed = int(d), int(nlist), int(seed)
+        self._flat = FlatL2Index(d, device=device)             # the fp32 rows in insertion order
+        self.device = self._flat.device
+        self._dev = _Dev(self.device)
+        self._nprobe = 1
+        self.centroids = None                                  # (nlist, d) float32 on the device
+        self._assign = self._dev.empty((0,), torch.int32)
+        self._lists = None
+
+    @property
+    def nprobe(self):
+        return self._nprobe
+
+    @nprobe.setter
+    def nprobe(self, v):
+        if not 1 <= int(v) <= MAX_NPROBE:
+            raise NotImplementedError(f'nprobe = {v} (the HIP IVF search keeps 1 .. {MAX_NPROBE} probes)')
+        self._nprobe = int(v)
+
+    @property
+    def is_trained(self):
+        return self.centroids is not None
+
+    @property
+    def ntotal(self):
+        return self._flat.ntotal
+
+    def _train_coarse(self, x, init):
+        n = len(x)
+        if n < self.nlist:
+            raise ValueError(f'{n} training points for nlist = {self.nlist} centroids (faiss refuses this too)')
+        rng = rng_for(self.seed, STREAM_COARSE)
+        idx = subset_indices(n, self.nlist * MAX_POINTS_PER_CENTROID, rng)
+        xt = _as_device(x if idx is None else _take(x, idx), self.device)
+        if init is None:
+            pick = rng.permutation(xt.shape[0])[:self.nlist]
+            cent = xt[torch.from_numpy(pick).to(self.device)].contiguous()
+        else:
+            cent = _as_device(init, self.device).clone()
+        dev = self._dev
+        dev.kmeans(xt, cent, self.nlist, 1, COARSE_ITERS, rng_for(self.seed, STREAM_COARSE_SPLIT), lambda c: (dev.assign(xt, c), 4))
+        self.centroids = cent
+
+    def probe_device(self, q):
+        """(nq, min(nprobe, nlist)) int32 CUDA: the probed lists per query, nearest first (ties: smaller list id)."""
+        q = _lib.require_cuda(q, 'q').float().contiguous()
+        npr = min(self._nprobe, self.nlist)
+        out = self._dev.empty((q.shape[0], npr), torch.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(self._dev.lib.nafp_ivf_probe(_lib.ptr(q), q.shape[0], _lib.ptr(self.centroids), self.nlist, self.d, npr, _lib.ptr(out),
+                                                    _lib.current_stream()), 'ivf_probe')
+        return out
+
+    def add(self, x):
+        if not self.is_trained:
+            raise RuntimeError('the index is not trained')
+        n0 = self.ntotal
+        self._flat.add(x)
+        n = self.ntotal - n0
+        if n == 0:
+            return
+        xd = self._flat._x[n0:n0 + n]
+        with torch.cuda.device(self.device):
+            a = self._dev.assign(xd, self.centroids)
+            self._add_encoded(xd, a)
+            self._assign = torch.cat([self._assign, a])
+        self._lists = None
+
+    def _add_encoded(self, xd, a):
+        pass
+
+    def _prepare(self):
+        if self._lists is None:
+            with torch.cuda.device(self.device):
+                offsets, ids = self._dev.bucket(self._assign, 4, self.ntotal, self.nlist, 1)
+                self._lists = self._build_lists(offsets.reshape(-1), ids.reshape(-1))
+        return self._lists
+
+    def search_device(self, q, k):
+        """q: (nq, d) CUDA float32 -> (D, I) CUDA tensors (float32, int32)."""
+        q = _lib.require_cuda(q, 'q').float().contiguous()
+        if k > MAX_K or k < 1:
+            raise NotImplementedError(f'k = {k} (the HIP search keeps k <= {MAX_K} results per query)')
+        if self.ntotal == 0:
+            raise ValueError('empty index')
+        lists = self._prepare()
+        nq = q.shape[0]
+        D = self._dev.empty((nq, k), torch.float32)
+        I = self._dev.empty((nq, k), torch.int32)
+        need = int(self._dev.lib.nafp_ivf_search_workspace_bytes(nq, self.nlist, self._nprobe, k, self.kind))
+        if need < 0:
+            raise NotImplementedError(f'k = {k}, nprobe = {self._nprobe}')
+        ws = self._dev.empty((need,), torch.uint8)
+        with torch.cuda.device(self.device):
+            self._search(q, k, lists, D, I, ws, need)
+        return D, I
+
+    def search(self, q, k):
+        """faiss signature: numpy in, (D float32, I int64) numpy out."""
+        qd = torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32)).to(self.device)
+        D, I = self.search_device(qd, k)
+        return D.cpu().numpy(), I.cpu().numpy().astype(np.int64)
+
+    def reconstruct_n(self, i0, n):
+        return self._flat.reconstruct_n(i0, n)
+
+    def sequence_scores(self, q, task_q0, task_len, cand):
+        """Scores from the original fp32 rows in insertion order (FlatL2Index.sequence_scores)."""
+        return self._flat.sequence_scores(q, task_q0, task_len, cand)
+
+    def list_assignments(self):
+        """(ntotal,) int32 CUDA: the list of every row, in insertion order."""
+        return self._assign
+
+    def lists(self):
+        """(offsets (nlist + 1,), ids (ntotal,)) int32 CUDA: the inverted lists, ascending ids inside each."""
+        L = self._prepare()
+        return L['offsets'], L['ids'][:self.ntotal]
+
+
+class IVFFlatIndex(_IVFBase):
+    """faiss.IndexIVFFlat(quantizer, d, nlist): rows stored as fp32 in their lists; exact squared L2 distances."""
+    kind = 0
+
+    def train(self, x, init=None):
+        """x: (n, d) numpy / memmap / CUDA tensor.  init: an explicit (nlist, d) k-means initialisation."""
+        self._train_coarse(x, init)
+
+    def set_params(self, centroids):
+        self.centroids = _as_device(centroids, self.device).clone()
+        self._lists = None
+
+    @property
+    def index_description(self):
+        return f'IVF-Flat (HIP; nlist {self.nlist}, nprobe {self._nprobe})'
+
+    def _build_lists(self, offsets, ids):
+        lib, n = self._dev.lib, self.ntotal
+        bound = int(lib.nafp_ivf_flat_rows_bound(n, self.nlist))
+        row_off = self._dev.empty((self.nlist + 1,), torch.int32)
+        rows = self._dev.empty((bound, self.d), torch.float32)
+        hn = self._dev.empty((bound,), torch.float32)
+        row_ids = self._dev.empty((bound,), torch.int32)
+        _lib.check(lib.nafp_ivf_flat_lists(_lib.ptr(self._flat._x), n, self.d, _lib.ptr(offsets), _lib.ptr(ids), self.nlist, _lib.ptr(row_off),
+                                           _lib.ptr(rows), _lib.ptr(hn), _lib.ptr(row_ids), _lib.current_stream()), 'ivf_flat_lists')
+        return dict(offsets=offsets, ids=ids, row_off=row_off, rows=rows, hn=hn, row_ids=row_ids)
+
+    def _search(self, q, k, L, D, I, ws, need):
+        _lib.check(self._dev.lib.nafp_ivf_flat_search(_lib.ptr(q), q.shape[0], _lib.ptr(self.centroids), self.nlist, self.d, self._nprobe,
+                                                      _lib.ptr(L['rows']), _lib.ptr(L['hn']), _lib.ptr(L['row_off']), _lib.ptr(L['row_ids']),
+                                                      int(k), _lib.ptr(D), _lib.ptr(I), _lib.ptr(ws), need, _lib.current_stream()),
+                   'ivf_flat_search')
+
+
+
+class IVFPQIndex(_IVFBase):
+    """faiss.IndexIVFPQ(quantizer, d, nlist, M, nbits) with by_residual: M = 64 sub-quantizers of 2^nbits = 256 codewords of
+    the residual to the coarse centroid; fp32 ADC tables (the reference's GPU index uses fp16 ones)."""
+    kind = 1
+
+    def __init__(self, d, nlist, M=64, nbits=8, seed=DEFAULT_SEED, device=None):
+        if M != 64 or nbits != 8 or d % M or d // M not in (1, 2, 4):
+            raise NotImplementedError(f'IVF-PQ with M = {M}, nbits = {nbits} (this build: M = 64, nbits = 8)')
+        super().__init__(d, nlist, seed, device)
+        self.M, self.nbits, self.dsub = int(M), int(nbits), d // M
+        self.pq_centroids = None                               # (M, 256, dsub) float32 on the device
+        self._codes = self._dev.empty((0, self.M), torch.uint8)
+
+    @property
+    def is_trained(self):
+        return self.centroids is not None and self.pq_centroids is not None
+
+    @property
+    def index_description(self):
+        return f'IVFPQ (HIP; nlist {self.nlist}, M {self.M}, nbits {self.nbits}, nprobe {self._nprobe})'
+
+    def set_params(self, centroids, pq_centroids):
+        self.centroids = _as_device(centroids, self.device).clone()
+        self.pq_centroids = _as_device(np.asarray(pq_centroids, dtype=np.float32).reshape(self.M, PQ_KS, self.dsub) if not torch.is_tensor(pq_centroids)
+                                       else pq_centroids.reshape(self.M, PQ_KS, self.dsub), self.device).clone()
+        self._lists = None
+
+    def train(self, x, init=None, pq_init=None):
+        """x: (n, d).  init: explicit (nlist, d) coarse initialisation; pq_init: explicit (M, 256, dsub) PQ initialisation."""
+        self._train_coarse(x, init)
+        rng = rng_for(self.seed, STREAM_PQ)
+        idx = subset_indices(len(x), PQ_MAX_TRAIN, rng)
+        xp = _as_device(x if idx is None else _take(x, idx), self.device)
+        dev = self._dev
+        with torch.cuda.device(self.device):
+            r = dev.residuals(xp, dev.assign(xp, self.centroids), self.centroids)
+            idx = subset_indices(r.shape[0], PQ_KS * MAX_POINTS_PER_CENTROID, rng)
+            if idx is not None:
+                r = r[torch.from_numpy(idx).to(self.device)].contiguous()
+            if pq_init is None:
+                if r.shape[0] < PQ_KS:
+                    raise ValueError(f'{r.shape[0]} training points for {PQ_KS} PQ centroids')
+                pick = torch.from_numpy(rng.permutation(r.shape[0])[:PQ_KS]).to(self.device)
+                pq = r[pick].reshape(PQ_KS, self.M, self.dsub).transpose(0, 1).contiguous()
+            else:
+                pq = _as_device(np.asarray(pq_init, dtype=np.float32).reshape(self.M, PQ_KS, self.dsub) if not torch.is_tensor(pq_init)
+                                else pq_init.reshape(self.M, PQ_KS, self.dsub), self.device).clone()
+            dev.kmeans(r, pq, PQ_KS, self.M, PQ_ITERS, rng_for(self.seed, STREAM_PQ_SPLIT), lambda c: (dev.pq_encode(r, None, None, c), 1))
+        self.pq_centroids = pq
+
+    def _add_encoded(self, xd, a):
+        self._codes = torch.cat([self._codes, self._dev.pq_encode(xd, a, self.centroids, self.pq_centroids)])
+
+    def codes(self):
+        """(ntotal, M) uint8 CUDA: the PQ codes in insertion order."""
+        return self._codes
+
+    def _build_lists(self, offsets, ids):
+        codes_sorted = self._dev.empty((self.ntotal, self.M), torch.uint8)
+        _lib.check(self._dev.lib.nafp_ivf_pq_lists(_lib.ptr(self._codes), self.ntotal, self.M, _lib.ptr(ids), _lib.ptr(codes_sorted),
+                                                   _lib.current_stream()), 'ivf_pq_lists')
+        return dict(offsets=offsets, ids=ids, codes=codes_sorted)
+
+    def _search(self, q, k, L, D, I, ws, need):
+        _lib.check(self._dev.lib.nafp_ivf_pq_search(_lib.ptr(q), q.shape[0], _lib.ptr(self.centroids), self.nlist, self.d, self._nprobe,
+                                                    _lib.ptr(self.pq_centroids), self.M, _lib.ptr(L['codes']), _lib.ptr(L['offsets']),
+                                                    _lib.ptr(L['ids']), int(k), _lib.ptr(D), _lib.ptr(I), _lib.ptr(ws), need,
+                                                    _lib.current_stream()), 'ivf_pq_search')

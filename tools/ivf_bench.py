@@ -1,0 +1,82 @@
+"""IVF-Flat / IVF-PQ against the exact search, on the device, nothing on disk (eval/ivf.py, csrc/ivf.hip).
+
+Data: N clustered synthetic fingerprints, d = 128, unit norm: 20 000 random unit centres, each row = normalise(centre +
+0.6 * unit Gaussian noise per row) (neighbouring rows of a centre sit at squared distance ~0.5, other centres at ~2, like
+fingerprints of one song against the rest); queries = nq random rows with noise (0.3 per row, normalised again) -- the noisy
+copies of eval_faiss.  Measures training time (the index's own seeded training subset), `add` rows/s with the rows already
+on the device, the lazy list build, search time for nq queries (k = 20, nprobe = 40) for the exact index, IVF-Flat
+(nlist 400) and IVF-PQ (nlist 256, M 64, nbits 8) in the same process, and 1-recall@1 / 1-recall@20 of both approximate
+indexes against the exact one (the exact nearest neighbour ranked first / within the top 20).
+
+usage: python tools/ivf_bench.py [N=10000000] [nq=38000] [reps=3]   (one JSON line at the end)"""
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from neural_audio_fp_amd.eval.eval_faiss import FlatL2Index  # noqa: E402
+from neural_audio_fp_amd.eval.ivf import IVFFlatIndex, IVFPQIndex  # noqa: E402
+
+N = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
+nq = int(sys.argv[2]) if len(sys.argv) > 2 else 38_000
+reps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+d, k, nprobe = 128, 20, 40
+
+
+def sync_time(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, out
+
+
+def best_search(idx, q):
+    idx.search_device(q[:256], k)
+    times = []
+    for _ in range(reps):
+        dt, out = sync_time(lambda: idx.search_device(q, k))
+        times.append(dt)
+    return min(times), out
+
+
+g = torch.Generator(device='cuda').manual_seed(0)
+centres = torch.nn.functional.normalize(torch.randn((20000, d), generator=g, device='cuda'), dim=1)
+x = torch.empty((N, d), device='cuda')
+step = 1 << 20
+for a in range(0, N, step):
+    b = min(N, a + step)
+    c = centres[torch.randint(0, 20000, (b - a,), generator=g, device='cuda')]
+    x[a:b] = torch.nn.functional.normalize(c + 0.6 * torch.randn((b - a, d), generator=g, device='cuda') / d ** 0.5, dim=1)
+pick = torch.randint(0, N, (nq,), generator=g, device='cuda')
+q = torch.nn.functional.normalize(x[pick] + 0.3 * torch.randn((nq, d), generator=g, device='cuda') / d ** 0.5, dim=1).contiguous()
+
+res = {'N': N, 'nq': nq, 'k': k, 'nprobe': nprobe, 'd': d}
+ex = FlatL2Index(d, capacity=N)
+ex.add(x)
+res['exact_search_s'], (_, Ie) = best_search(ex, q)
+print(f'exact: search {res["exact_search_s"]:.3f} s', flush=True)
+del ex
+
+for name, make in (('ivf', lambda: IVFFlatIndex(d, 400)), ('ivfpq', lambda: IVFPQIndex(d, 256, 64, 8))):
+    idx = make()
+    idx.nprobe = nprobe
+    res[f'{name}_train_s'], _ = sync_time(lambda: idx.train(x))
+    res[f'{name}_add_s'], _ = sync_time(lambda: idx.add(x))
+    res[f'{name}_lists_s'], _ = sync_time(idx._prepare)
+    res[f'{name}_add_rows_per_s'] = N / res[f'{name}_add_s']
+    res[f'{name}_search_s'], (_, Ia) = best_search(idx, q)
+    res[f'{name}_search_vs_exact'] = res[f'{name}_search_s'] / res['exact_search_s']
+    nn = Ie[:, :1]
+    res[f'{name}_recall_at_1'] = float((Ia[:, :1] == nn).float().mean())
+    res[f'{name}_recall_at_20'] = float((Ia == nn).any(1).float().mean())
+    print(f'{name}: train {res[f"{name}_train_s"]:.2f} s, add {res[f"{name}_add_s"]:.3f} s ({res[f"{name}_add_rows_per_s"] / 1e6:.1f} M rows/s) '
+          f'+ lists {res[f"{name}_lists_s"]:.3f} s, search {res[f"{name}_search_s"]:.3f} s ({res[f"{name}_search_vs_exact"]:.2f} x exact), '
+          f'1-recall@1 {res[f"{name}_recall_at_1"]:.4f}, @20 {res[f"{name}_recall_at_20"]:.4f}', flush=True)
+    del idx
+    torch.cuda.empty_cache()
+print(json.dumps(res))

@@ -474,8 +474,8 @@ int nafp_search_seq_scores(const float* query, const float* index, int64_t n_ind
  * Ties everywhere: the smaller id (list, code, row) first.  All pointers are device pointers; results
  * are bit-identical from run to run and do not depend on how rows or queries are batched.
  * Status: NAFP_ERR_INVALID_ARG for a null pointer or a negative size, NAFP_ERR_UNSUPPORTED for a dim
- * outside 64 / 128 / 256, k > 32, nprobe > 128, M != 64 or n_buckets / nlist > 16384; checked before
- * any GPU call.  The *_workspace_bytes queries return -1 for such arguments.
+ * outside 64 / 128 / 256, k > 32, nprobe > 128, M != 64, n_buckets / nlist > 16384 or an unknown lut;
+ * checked before any GPU call.  The *_workspace_bytes queries return -1 for such arguments.
  * ------------------------------------------------------------------------------------------- */
 
 /* Stable counting sort of `batch` key arrays: key (b, i) = keys[i * batch + b] (int32 or uint8 by
@@ -523,12 +523,39 @@ int nafp_ivf_flat_search(const float* query, int64_t n_query, const float* centr
                          int nprobe, const float* rows, const float* half_norms, const int32_t* row_offsets,
                          const int32_t* row_ids, int k, float* out_dist, int32_t* out_ids, void* workspace,
                          int64_t workspace_bytes, void* stream);
-/* The same with the fp32 ADC distance sum_m |(q - c_list)_m - P[m][code_m]|^2 (codes_sorted / offsets /
- * ids: the lists as nafp_ivf_pq_lists and nafp_ivf_bucket leave them). */
+/* The same with the ADC distance sum_m |(q - c_list)_m - P[m][code_m]|^2 from fp32 tables (codes_sorted /
+ * offsets / ids: the lists as nafp_ivf_pq_lists and nafp_ivf_bucket leave them). */
 int nafp_ivf_pq_search(const float* query, int64_t n_query, const float* centroids, int nlist, int dim, int nprobe,
                        const float* pq_centroids, int M, const uint8_t* codes_sorted, const int32_t* offsets,
                        const int32_t* ids, int k, float* out_dist, int32_t* out_ids, void* workspace,
                        int64_t workspace_bytes, void* stream);
+
+/* Precision of the IVF-PQ ADC (asymmetric distance) lookup tables.  Entry T[m][c] of the table of a (query,
+ * list) pair is computed in fp32 either way: residual rr = q - centroids[list], then sum_u (rr[m * dsub + u] -
+ * P[m][c][u])^2 with u ascending.
+ *   NAFP_IVF_LUT_F32  the entries are kept as they are (the default everywhere).
+ *   NAFP_IVF_LUT_F16  each entry is rounded ONCE to IEEE binary16, round to nearest even, gradual underflow
+ *                     kept (with dim / M = 1 or 2 many entries are fp16 subnormals) -- the lookup tables of the
+ *                     reference's GPU index (faiss useFloat16).  Entries above the binary16 range (65504) are
+ *                     outside the contract; fingerprints are unit vectors, so real entries are at most 4.
+ * Either way a row's distance is the sum over m = 0 .. 63, in that order, of its entries widened to fp32
+ * and added in fp32; ties: the smaller id first. */
+#define NAFP_IVF_LUT_F32 0
+#define NAFP_IVF_LUT_F16 1
+
+/* nafp_ivf_pq_search with the table precision chosen; lut = NAFP_IVF_LUT_F32 is nafp_ivf_pq_search, byte for
+ * byte.  Workspace: nafp_ivf_search_workspace_bytes(..., kind 1), for either value. */
+int nafp_ivf_pq_search_ex(const float* query, int64_t n_query, const float* centroids, int nlist, int dim,
+                          int nprobe, const float* pq_centroids, int M, const uint8_t* codes_sorted,
+                          const int32_t* offsets, const int32_t* ids, int k, float* out_dist, int32_t* out_ids,
+                          int lut, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The ADC tables themselves, as the search builds them, for n_pairs (query row, list) pairs given as two
+ * device int32 arrays: out is (n_pairs, M, 256) float32 (lut 0) or binary16 (lut 1).  A pair that names a row
+ * outside [0, n_query) or a list outside [0, nlist) gets NaNs.  A building block (re-use, tests). */
+int nafp_ivf_pq_adc_tables(const float* query, int64_t n_query, const int32_t* pair_query,
+                           const int32_t* pair_list, int64_t n_pairs, const float* centroids, int nlist, int dim,
+                           const float* pq_centroids, int M, int lut, void* out, void* stream);
 
 /* In-training mini search test (model/utils/mini_search_subroutines.py): pairwise_distances_for_eval (:28-93;
  * mode 0 = squared L2 clipped at 0 for 'argmin', 1 = dot product for 'argmax'; any dim) into out_scores

@@ -19,8 +19,16 @@
 //   ivf_pq_scan_kernel<DSUB,K> per (query, list) pair: the fp32 ADC table (64 x 256, 64 KB of LDS), then the list's 64-byte
 //                              codes, 64 LDS lookups per row, summed in sub-space order; register top-K per lane, then a
 //                              workgroup-wide K-way selection
+//   ivf_pq_scan_f16_kernel<DSUB,K>  the same with the table rounded once to binary16 (NAFP_IVF_LUT_F16, the reference's
+//                              useFloat16 lookup tables): 32 KB of table, entries widened to fp32 and summed in fp32 in
+//                              sub-space order.  The selection does not go through the table area: each wave reduces its 64
+//                              lane lists in registers (K rounds of a wave arg-max of the heads, the winner shifts its list),
+//                              then the 4 x K wave results are ranked by counting -- 34 KB of LDS in all, four workgroups per CU
+//   ivf_pq_adc_tables_kernel<DSUB,LUT>  the tables themselves for given (query, list) pairs (ivf_adc_entry, as the scans)
 //   ivf_merge_kernel           per query: the probes' partial lists -> k results (distance asc, id asc), -1 / +inf padding
 #include "nafp_common.h"
+
+#include <hip/hip_fp16.h>
 
 #include <algorithm>
 
@@ -281,6 +289,31 @@ __global__ void ivf_qblock_prefix_kernel(const int* __restrict__ pair_off, int n
     qblk_off[nlist] = run;
 }
 
+// ADC table entry e = m * 256 + c of the residual rr (fp32, D entries): sum_u (rr[m * DSUB + u] - P[m][c][u])^2, u ascending.
+// The one place the table is computed: both scans and the export call it.
+template <int DSUB>
+__device__ __forceinline__ float ivf_adc_entry(const float* rr, const float* __restrict__ pq, int e) {
+    const int m = e >> 8;
+    const float* c = pq + (int64_t)e * DSUB;
+    float s = 0.f;
+#pragma unroll
+    for (int u = 0; u < DSUB; ++u) { const float t = rr[m * DSUB + u] - c[u]; s += t * t; }
+    return s;
+}
+
+// sorted insert into a lane's descending (sc, id) list; the caller has checked key > sc[K - 1].  Rows ascend within the
+// lane, so the strict comparisons keep the smaller id first among equal keys.
+template <int K>
+__device__ __forceinline__ void ivf_topk_insert(float (&sc)[K], int (&id)[K], float key, int nid) {
+#pragma unroll
+    for (int j = K - 1; j >= 1; --j) {
+        const bool cj = key > sc[j], cp2 = key > sc[j - 1];
+        id[j] = cj ? (cp2 ? id[j - 1] : nid) : id[j];
+        sc[j] = cj ? (cp2 ? sc[j - 1] : key) : sc[j];
+    }
+    if (key > sc[0]) { sc[0] = key; id[0] = nid; }
+}
+
 // one workgroup per (pair, part): ADC table of the pair in LDS, then rows [r0, r1) of the list's part
 template <int DSUB, int K>
 __global__ __launch_bounds__(256) void ivf_pq_scan_kernel(const float* __restrict__ Q, const int* __restrict__ qmap,
@@ -298,14 +331,7 @@ __global__ __launch_bounds__(256) void ivf_pq_scan_kernel(const float* __restric
     const int q = qmap[pos], l = plist[pos];
     for (int dd = tid; dd < D; dd += 256) rr[dd] = Q[(int64_t)q * D + dd] - coarse[(int64_t)l * D + dd];
     __syncthreads();
-    for (int e = tid; e < NT; e += 256) {
-        const int m = e >> 8;
-        const float* c = pq + (int64_t)e * DSUB;
-        float s = 0.f;
-#pragma unroll
-        for (int u = 0; u < DSUB; ++u) { const float t = rr[m * DSUB + u] - c[u]; s += t * t; }
-        lut[e] = s;
-    }
+    for (int e = tid; e < NT; e += 256) lut[e] = ivf_adc_entry<DSUB>(rr, pq, e);
     __syncthreads();
     const int o0 = off[l];
     const int len = off[l + 1] - o0;
@@ -331,16 +357,7 @@ __global__ __launch_bounds__(256) void ivf_pq_scan_kernel(const float* __restric
 #pragma unroll
         for (int m = 0; m < PQ_M; ++m) s += lut[m * PQ_KS + ((w[m >> 2] >> (8 * (m & 3))) & 255u)];
         const float key = -s;
-        if (key > sc[K - 1]) {                                    // rows ascend within the lane: ties keep the smaller id
-            const int nid = ids[o0 + r];
-#pragma unroll
-            for (int j = K - 1; j >= 1; --j) {
-                const bool cj = key > sc[j], cp2 = key > sc[j - 1];
-                id[j] = cj ? (cp2 ? id[j - 1] : nid) : id[j];
-                sc[j] = cj ? (cp2 ? sc[j - 1] : key) : sc[j];
-            }
-            if (key > sc[0]) { sc[0] = key; id[0] = nid; }
-        }
+        if (key > sc[K - 1]) ivf_topk_insert<K>(sc, id, key, ids[o0 + r]);
     }
     // workgroup top-K: the 256 sorted lane lists in LDS (the table is done), K rounds of a workgroup-wide arg-max of the heads
     __syncthreads();
@@ -365,6 +382,109 @@ __global__ __launch_bounds__(256) void ivf_pq_scan_kernel(const float* __restric
             pi[o + j] = best ? ivf_unpack_id(best) : -1;
         }
         __syncthreads();
+    }
+}
+
+// The same scan with the table in binary16 (NAFP_IVF_LUT_F16).  Entry: ivf_adc_entry in fp32, rounded once (nearest even,
+// subnormals kept: v_cvt_f16_f32 follows the f16 denormal mode, which is on); a row's distance: the 64 entries widened to fp32
+// and added in fp32, m ascending.  Table layout: plain [m][c] halves, i.e. codes c and c ^ 1 share a dword and dword c / 2 of a
+// sub-table sits on bank (c / 2) % 32.  A lookup instruction reads ONE sub-table for all lanes (same m, the lanes' own
+// codes), and the codes of different rows are unrelated, so any placement of the 256 entries on 128 dwords puts 4 dwords on
+// each bank and meets the same conflicts; this one needs no address arithmetic beyond c * 2 (m * 512 is the instruction's
+// offset) and its table fill is conflict-free.  Lanes with equal or paired codes read one dword (broadcast).
+// LDS: 32 KB table + 1 KB residual + 4 * K * 8 B wave results = 34 432 / 34 816 B (K = 20 / 32): four workgroups per CU
+// (16 waves, 4 per SIMD); the registers allow that (83 / 116 VGPRs, build/ivf.resources.txt).
+template <int DSUB, int K>
+__global__ __launch_bounds__(256) void ivf_pq_scan_f16_kernel(const float* __restrict__ Q, const int* __restrict__ qmap,
+                                                              const int* __restrict__ plist, const float* __restrict__ coarse,
+                                                              const float* __restrict__ pq, const unsigned char* __restrict__ codes,
+                                                              const int* __restrict__ off, const int* __restrict__ ids, int parts,
+                                                              float* __restrict__ pk, int* __restrict__ pi) {
+    constexpr int D = PQ_M * DSUB, NT = PQ_M * PQ_KS;
+    extern __shared__ __attribute__((aligned(16))) float lds_f16[];    // [NT] halves, then [256] residual, [4 * K] x u64 wave results
+    __half* lut = (__half*)lds_f16;
+    float* rr = lds_f16 + NT / 2;
+    unsigned long long* wres = (unsigned long long*)(rr + 256);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t pos = blockIdx.x;
+    const int part = blockIdx.y;
+    const int q = qmap[pos], l = plist[pos];
+    for (int dd = tid; dd < D; dd += 256) rr[dd] = Q[(int64_t)q * D + dd] - coarse[(int64_t)l * D + dd];
+    __syncthreads();
+    for (int e = tid; e < NT; e += 256) lut[e] = __float2half_rn(ivf_adc_entry<DSUB>(rr, pq, e));
+    __syncthreads();
+    const int o0 = off[l];
+    const int len = off[l + 1] - o0;
+    const int per = (len + parts - 1) / parts;
+    const int r0 = std::min(len, part * per), r1 = std::min(len, r0 + per);
+    float sc[K]; int id[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) { sc[j] = -INFINITY; id[j] = -1; }
+    uint4 n0 = make_uint4(0u, 0u, 0u, 0u), n1 = n0, n2 = n0, n3 = n0;     // the next row's codes, loaded a row ahead
+    if (r0 + tid < r1) {
+        const uint4* cp = (const uint4*)(codes + (int64_t)(o0 + r0 + tid) * PQ_M);
+        n0 = cp[0]; n1 = cp[1]; n2 = cp[2]; n3 = cp[3];
+    }
+    for (int r = r0 + tid; r < r1; r += 256) {
+        const uint4 w0 = n0, w1 = n1, w2 = n2, w3 = n3;
+        if (r + 256 < r1) {
+            const uint4* cp = (const uint4*)(codes + (int64_t)(o0 + r + 256) * PQ_M);
+            n0 = cp[0]; n1 = cp[1]; n2 = cp[2]; n3 = cp[3];
+        }
+        const unsigned w[16] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w, w3.x, w3.y, w3.z, w3.w};
+        float s = 0.f;
+#pragma unroll
+        for (int m = 0; m < PQ_M; ++m) s += __half2float(lut[m * PQ_KS + ((w[m >> 2] >> (8 * (m & 3))) & 255u)]);
+        const float key = -s;
+        if (key > sc[K - 1]) ivf_topk_insert<K>(sc, id, key, ids[o0 + r]);
+    }
+    // wave top-K in registers: K rounds of a wave-wide arg-max of the lanes' heads; the winning lane drops its head (a shift
+    // by one with static indices: no scratch).  Packed values are distinct (ids are), 0 = nothing left.
+#pragma unroll 1
+    for (int j = 0; j < K; ++j) {
+        const unsigned long long v = id[0] >= 0 ? ivf_pack(sc[0], id[0]) : 0ull;
+        unsigned long long b = v;
+#pragma unroll
+        for (int s2 = 32; s2 > 0; s2 >>= 1) { const unsigned long long ob = __shfl_xor(b, s2, 64); b = ob > b ? ob : b; }
+        if (lane == 0) wres[wave * K + j] = b;
+        if (b != 0ull && v == b) {
+#pragma unroll
+            for (int i = 0; i < K - 1; ++i) { sc[i] = sc[i + 1]; id[i] = id[i + 1]; }
+            sc[K - 1] = -INFINITY; id[K - 1] = -1;
+        }
+    }
+    __syncthreads();
+    // the 4 x K wave results ranked by counting (distinct values): rank < K goes out, the rest of the K slots is padding
+    const int64_t o = (pos * parts + part) * K;
+    if (tid < 4 * K) {
+        const unsigned long long v = wres[tid];
+        int rank = 0, filled = 0;
+#pragma unroll 4
+        for (int i = 0; i < 4 * K; ++i) { const unsigned long long u = wres[i]; rank += u > v ? 1 : 0; filled += u != 0ull ? 1 : 0; }
+        if (v != 0ull && rank < K) { pk[o + rank] = ivf_unpack_key(v); pi[o + rank] = ivf_unpack_id(v); }
+        if (tid < K && tid >= filled) { pk[o + tid] = -INFINITY; pi[o + tid] = -1; }
+    }
+}
+
+// the ADC table of pair p = (query pair_query[p], list pair_list[p]) as the scans build it: out (n_pairs, 64, 256) fp32 (LUT 0)
+// or binary16 (LUT 1).  A pair that names a query or a list outside the arrays gets NaNs (nothing is read for it).
+template <int DSUB, int LUT>
+__global__ __launch_bounds__(256) void ivf_pq_adc_tables_kernel(const float* __restrict__ Q, int64_t n_query, const int* __restrict__ pair_query,
+                                                                const int* __restrict__ pair_list, const float* __restrict__ coarse, int nlist,
+                                                                const float* __restrict__ pq, void* __restrict__ out) {
+    constexpr int D = PQ_M * DSUB, NT = PQ_M * PQ_KS;
+    __shared__ float rr[256];
+    const int tid = threadIdx.x;
+    const int64_t p = blockIdx.x;
+    const int q = pair_query[p], l = pair_list[p];
+    const bool ok = q >= 0 && q < n_query && l >= 0 && l < nlist;
+    if (ok)
+        for (int dd = tid; dd < D; dd += 256) rr[dd] = Q[(int64_t)q * D + dd] - coarse[(int64_t)l * D + dd];
+    __syncthreads();
+    for (int e = tid; e < NT; e += 256) {
+        const float s = ok ? ivf_adc_entry<DSUB>(rr, pq, e) : NAN;
+        if (LUT == 0) ((float*)out)[p * NT + e] = s;
+        else          ((__half*)out)[p * NT + e] = __float2half_rn(s);
     }
 }
 
@@ -627,37 +747,73 @@ extern "C" int nafp_ivf_flat_search(const float* query, int64_t n_query, const f
     return ivf_search_merge(L, ws, n_query, row_ids, row_offsets, query, dim, 0, out_dist, out_ids, k, st);
 }
 
-extern "C" int nafp_ivf_pq_search(const float* query, int64_t n_query, const float* centroids, int nlist, int dim, int nprobe,
-                                  const float* pq_centroids, int M, const uint8_t* codes_sorted, const int32_t* offsets,
-                                  const int32_t* ids, int k, float* out_dist, int32_t* out_ids, void* workspace, int64_t workspace_bytes,
-                                  void* stream) {
+static bool ivf_lut_ok(int lut) { return lut == NAFP_IVF_LUT_F32 || lut == NAFP_IVF_LUT_F16; }
+
+extern "C" int nafp_ivf_pq_search_ex(const float* query, int64_t n_query, const float* centroids, int nlist, int dim, int nprobe,
+                                     const float* pq_centroids, int M, const uint8_t* codes_sorted, const int32_t* offsets,
+                                     const int32_t* ids, int k, float* out_dist, int32_t* out_ids, int lut, void* workspace,
+                                     int64_t workspace_bytes, void* stream) {
     if (!query || !centroids || !pq_centroids || !codes_sorted || !offsets || !ids || !out_dist || !out_ids || !workspace ||
         n_query < 0 || nlist <= 0 || nprobe <= 0 || k <= 0)
         return NAFP_ERR_INVALID_ARG;
     IvfSearchLayout L;
-    if (!ivf_dim_ok(dim) || M != PQ_M || !ivf_search_layout(n_query, nlist, nprobe, k, 1, &L)) return NAFP_ERR_UNSUPPORTED;
+    if (!ivf_dim_ok(dim) || M != PQ_M || !ivf_lut_ok(lut) || !ivf_search_layout(n_query, nlist, nprobe, k, 1, &L)) return NAFP_ERR_UNSUPPORTED;
     if (n_query == 0) return NAFP_OK;
     if (workspace_bytes < L.total) return NAFP_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
     int rc = ivf_search_front(query, n_query, centroids, nlist, dim, L, ws, st);
     if (rc != NAFP_OK) return rc;
-    const int lds = (PQ_M * PQ_KS + 256) * 4 + 4 * 8;
+    // fp32: table + residual + 4 wave bests; fp16: half the table + residual + 4 x K wave results
+    const int lds = lut == NAFP_IVF_LUT_F32 ? (PQ_M * PQ_KS + 256) * 4 + 4 * 8 : PQ_M * PQ_KS * 2 + 256 * 4 + 4 * L.K * 8;
     const dim3 grid((unsigned)L.n_pairs, (unsigned)L.parts);
     const int* qm = (const int*)(ws + L.o_qmap);
     const int* pl = (const int*)(ws + L.o_plist);
     float* pk = (float*)(ws + L.o_pk);
     int* pi = (int*)(ws + L.o_pi);
-#define NAFP_PQ_SCAN(DS_, K_)                                                                                                   \
+#define NAFP_PQ_SCAN(KERNEL_, DS_, K_)                                                                                          \
     {                                                                                                                           \
-        NAFP_HIP_CHECK(hipFuncSetAttribute((const void*)ivf_pq_scan_kernel<DS_, K_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); \
-        ivf_pq_scan_kernel<DS_, K_><<<grid, 256, lds, st>>>(query, qm, pl, centroids, pq_centroids, codes_sorted, offsets, ids,    \
-                                                            L.parts, pk, pi);                                                    \
+        NAFP_HIP_CHECK(hipFuncSetAttribute((const void*)KERNEL_<DS_, K_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));       \
+        KERNEL_<DS_, K_><<<grid, 256, lds, st>>>(query, qm, pl, centroids, pq_centroids, codes_sorted, offsets, ids, L.parts, pk, pi); \
     }
+#define NAFP_PQ_SCAN_K(KERNEL_, DS_) { if (L.K == 20) NAFP_PQ_SCAN(KERNEL_, DS_, 20) else NAFP_PQ_SCAN(KERNEL_, DS_, 32) }
+#define NAFP_PQ_SCAN_D(KERNEL_)                                                                                                 \
+    { if (dsub == 1) NAFP_PQ_SCAN_K(KERNEL_, 1) else if (dsub == 2) NAFP_PQ_SCAN_K(KERNEL_, 2) else NAFP_PQ_SCAN_K(KERNEL_, 4) }
     const int dsub = dim / PQ_M;
-    if (L.K == 20) { if (dsub == 1) NAFP_PQ_SCAN(1, 20) else if (dsub == 2) NAFP_PQ_SCAN(2, 20) else NAFP_PQ_SCAN(4, 20) }
-    else           { if (dsub == 1) NAFP_PQ_SCAN(1, 32) else if (dsub == 2) NAFP_PQ_SCAN(2, 32) else NAFP_PQ_SCAN(4, 32) }
+    if (lut == NAFP_IVF_LUT_F32) NAFP_PQ_SCAN_D(ivf_pq_scan_kernel) else NAFP_PQ_SCAN_D(ivf_pq_scan_f16_kernel)
+#undef NAFP_PQ_SCAN_D
+#undef NAFP_PQ_SCAN_K
 #undef NAFP_PQ_SCAN
     NAFP_LAUNCH_CHECK();
     return ivf_search_merge(L, ws, n_query, nullptr, nullptr, query, dim, 1, out_dist, out_ids, k, st);
+}
+
+extern "C" int nafp_ivf_pq_search(const float* query, int64_t n_query, const float* centroids, int nlist, int dim, int nprobe,
+                                  const float* pq_centroids, int M, const uint8_t* codes_sorted, const int32_t* offsets,
+                                  const int32_t* ids, int k, float* out_dist, int32_t* out_ids, void* workspace, int64_t workspace_bytes,
+                                  void* stream) {
+    return nafp_ivf_pq_search_ex(query, n_query, centroids, nlist, dim, nprobe, pq_centroids, M, codes_sorted, offsets, ids, k, out_dist,
+                                 out_ids, NAFP_IVF_LUT_F32, workspace, workspace_bytes, stream);
+}
+
+extern "C" int nafp_ivf_pq_adc_tables(const float* query, int64_t n_query, const int32_t* pair_query, const int32_t* pair_list,
+                                      int64_t n_pairs, const float* centroids, int nlist, int dim, const float* pq_centroids, int M, int lut,
+                                      void* out, void* stream) {
+    if (!query || !pair_query || !pair_list || !centroids || !pq_centroids || !out || n_query < 0 || n_pairs < 0 || nlist <= 0)
+        return NAFP_ERR_INVALID_ARG;
+    if (!ivf_dim_ok(dim) || M != PQ_M || !ivf_lut_ok(lut) || nlist > IVF_MAX_BUCKETS || n_query > (1 << 30) || n_pairs >= ((int64_t)1 << 31))
+        return NAFP_ERR_UNSUPPORTED;
+    if (n_pairs == 0) return NAFP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned grid = (unsigned)n_pairs;
+#define NAFP_PQ_TABLES(DS_)                                                                                                     \
+    {                                                                                                                           \
+        if (lut == NAFP_IVF_LUT_F32) ivf_pq_adc_tables_kernel<DS_, 0><<<grid, 256, 0, st>>>(query, n_query, pair_query, pair_list, centroids, nlist, pq_centroids, out); \
+        else                         ivf_pq_adc_tables_kernel<DS_, 1><<<grid, 256, 0, st>>>(query, n_query, pair_query, pair_list, centroids, nlist, pq_centroids, out); \
+    }
+    const int dsub = dim / PQ_M;
+    if (dsub == 1) NAFP_PQ_TABLES(1) else if (dsub == 2) NAFP_PQ_TABLES(2) else NAFP_PQ_TABLES(4)
+#undef NAFP_PQ_TABLES
+    NAFP_LAUNCH_CHECK();
+    return NAFP_OK;
 }

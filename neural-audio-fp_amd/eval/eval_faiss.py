@@ -4,7 +4,8 @@ Host mirror of the reference's eval/eval_faiss.py (`load_memmap_data` :18-62, `e
 and of `get_index` (eval/utils/get_index_faiss.py:10-121) for index_type 'L2' -- the exact
 faiss.IndexFlatL2 -- backed by libnafp's search kernels (include/nafp.h "Search / evaluation").
 With NAFP_APPROX_INDEX=1 in the environment, 'ivf' and 'ivfpq' build real IVF-Flat / IVF-PQ indexes on the device (eval/ivf.py,
-opt-in; `index_used.json` then names the index and its parameters).  Otherwise, and always for IVFPQ-RR, IVFPQ-ONDISK and HNSW,
+opt-in; `index_used.json` then names the index and its parameters; NAFP_IVFPQ_LUT=f16 gives 'ivfpq' the reference's fp16 lookup
+tables).  Otherwise, and always for IVFPQ-RR, IVFPQ-ONDISK and HNSW,
 the approximate index types are not built: a request for one of them
 (the reference's default is `-i ivfpq`) is SERVED BY THE EXACT SEARCH, with a notice on stderr and the substitution
 recorded in `index_used.json` next to `raw_score.npy` -- on an MI355X the whole [dummy_db ; db] table stays resident
@@ -139,6 +140,15 @@ def approx_index_enabled():
     return os.environ.get('NAFP_APPROX_INDEX', '') == '1'
 
 
+def ivfpq_lut():
+    """NAFP_IVFPQ_LUT: the ADC table precision of the opted-in 'ivfpq' index, 'f32' (default) or 'f16' (the reference's
+    useFloat16 lookup tables)."""
+    lut = os.environ.get('NAFP_IVFPQ_LUT', '') or 'f32'
+    if lut not in ('f32', 'f16'):
+        raise ValueError(f"NAFP_IVFPQ_LUT = {lut!r} ('f32' or 'f16')")
+    return lut
+
+
 def get_index(index_type, train_data, train_data_shape, use_gpu=True, max_nitem_train=2e7):
     """get_index_faiss.py:10-121 for the exact index (and, opted in, IVF / IVFPQ)."""
     mode = index_type.lower()
@@ -152,7 +162,7 @@ def get_index(index_type, train_data, train_data_shape, use_gpu=True, max_nitem_
         from .ivf import IVFFlatIndex, IVFPQIndex, training_subset
         p = APPROX_INDEX_PARAMS[mode]
         d = int(train_data_shape[1])
-        index = IVFFlatIndex(d, p['nlist']) if mode == 'ivf' else IVFPQIndex(d, p['nlist'], p['M'], p['nbits'])
+        index = IVFFlatIndex(d, p['nlist']) if mode == 'ivf' else IVFPQIndex(d, p['nlist'], p['M'], p['nbits'], lut=ivfpq_lut())
         index.nprobe = p['nprobe']
         start_time = time.time()
         index.train(training_subset(train_data, max_nitem_train, index.seed))

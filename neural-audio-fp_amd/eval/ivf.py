@@ -5,7 +5,9 @@ evaluation (eval/utils/get_index_faiss.py:64-80, nprobe = 40 at :120), backed by
 faiss-shaped surface: `train(x)`, `is_trained`, `add(x)` (repeatedly), `ntotal`, a settable `nprobe`, `search(q, k)` ->
 (D, I) numpy, `search_device`; plus what the evaluation needs (`device`, `sequence_scores`, `reconstruct_n`: the original fp32
 rows in insertion order, kept in a FlatL2Index -- the reference's `fake_recon_index`) and, for tests and re-use, `centroids`,
-`pq_centroids`, `probe_device(q)` and `set_params(...)` / explicit k-means initialisations in `train`.
+`pq_centroids`, `probe_device(q)` and `set_params(...)` / explicit k-means initialisations in `train`.  IVF-PQ has a settable
+`lut` ('f32', the default, or 'f16': the ADC tables rounded to binary16 as the reference's GPU index keeps them) and
+`adc_tables(q, pair_query, pair_list)`, the tables themselves.
 
 Training is modelled on faiss's CPU defaults (documentation and source as publicly known; faiss is not a dependency, so this is
 the project's contract rather than a checked copy).  Every constant of it is below.  torch only allocates and copies here; the
@@ -26,6 +28,7 @@ SPLIT_EPS = 1.0 / 1024                   # empty-cluster split: the two copies a
 MAX_NPROBE = 128
 MAX_K = 32
 MAX_NLIST = 16384
+LUT_CODES = {'f32': 0, 'f16': 1}         # NAFP_IVF_LUT_F32 / NAFP_IVF_LUT_F16 (include/nafp.h)
 ASSIGN_CHUNK = 1 << 20                   # rows per coarse-assignment launch (the exact kernel's workspace grows with them)
 
 # independent random streams of one seed
@@ -332,12 +335,15 @@ class IVFFlatIndex(_IVFBase):
 
 class IVFPQIndex(_IVFBase):
     """faiss.IndexIVFPQ(quantizer, d, nlist, M, nbits) with by_residual: M = 64 sub-quantizers of 2^nbits = 256 codewords of
-    the residual to the coarse centroid; fp32 ADC tables (the reference's GPU index uses fp16 ones)."""
+    the residual to the coarse centroid.  `lut`: the precision of the ADC tables of a search, 'f32' (default) or 'f16' (the
+    reference's GPU index, useFloat16; contract in include/nafp.h).  It can be changed at any time: centroids, codes
+    and lists do not depend on it."""
     kind = 1
 
-    def __init__(self, d, nlist, M=64, nbits=8, seed=DEFAULT_SEED, device=None):
+    def __init__(self, d, nlist, M=64, nbits=8, seed=DEFAULT_SEED, device=None, lut='f32'):
         if M != 64 or nbits != 8 or d % M or d // M not in (1, 2, 4):
             raise NotImplementedError(f'IVF-PQ with M = {M}, nbits = {nbits} (this build: M = 64, nbits = 8)')
+        self.lut = lut
         super().__init__(d, nlist, seed, device)
         self.M, self.nbits, self.dsub = int(M), int(nbits), d // M
         self.pq_centroids = None                               # (M, 256, dsub) float32 on the device
@@ -348,8 +354,19 @@ class IVFPQIndex(_IVFBase):
         return self.centroids is not None and self.pq_centroids is not None
 
     @property
+    def lut(self):
+        return self._lut
+
+    @lut.setter
+    def lut(self, v):
+        if v not in LUT_CODES:
+            raise ValueError(f'lut = {v!r} (the ADC tables are {" or ".join(map(repr, LUT_CODES))})')
+        self._lut = v
+
+    @property
     def index_description(self):
-        return f'IVFPQ (HIP; nlist {self.nlist}, M {self.M}, nbits {self.nbits}, nprobe {self._nprobe})'
+        tables = ', fp16 tables' if self._lut == 'f16' else ''
+        return f'IVFPQ (HIP; nlist {self.nlist}, M {self.M}, nbits {self.nbits}, nprobe {self._nprobe}{tables})'
 
     def set_params(self, centroids, pq_centroids):
         self.centroids = _as_device(centroids, self.device).clone()
@@ -394,7 +411,23 @@ class IVFPQIndex(_IVFBase):
         return dict(offsets=offsets, ids=ids, codes=codes_sorted)
 
     def _search(self, q, k, L, D, I, ws, need):
-        _lib.check(self._dev.lib.nafp_ivf_pq_search(_lib.ptr(q), q.shape[0], _lib.ptr(self.centroids), self.nlist, self.d, self._nprobe,
-                                                    _lib.ptr(self.pq_centroids), self.M, _lib.ptr(L['codes']), _lib.ptr(L['offsets']),
-                                                    _lib.ptr(L['ids']), int(k), _lib.ptr(D), _lib.ptr(I), _lib.ptr(ws), need,
-                                                    _lib.current_stream()), 'ivf_pq_search')
+        _lib.check(self._dev.lib.nafp_ivf_pq_search_ex(_lib.ptr(q), q.shape[0], _lib.ptr(self.centroids), self.nlist, self.d, self._nprobe,
+                                                       _lib.ptr(self.pq_centroids), self.M, _lib.ptr(L['codes']), _lib.ptr(L['offsets']),
+                                                       _lib.ptr(L['ids']), int(k), _lib.ptr(D), _lib.ptr(I), LUT_CODES[self._lut],
+                                                       _lib.ptr(ws), need, _lib.current_stream()), 'ivf_pq_search_ex')
+
+    def adc_tables(self, q, pair_query, pair_list):
+        """The ADC tables the search builds for the pairs (query row pair_query[p] of q, list pair_list[p]): (n_pairs, M, 256) CUDA,
+        float32 or float16 by `lut`."""
+        q = _lib.require_cuda(q, 'q').float().contiguous()
+        pq_, pl_ = (torch.as_tensor(np.asarray(t) if not torch.is_tensor(t) else t).to(device=self.device, dtype=torch.int32).contiguous()
+                    for t in (pair_query, pair_list))
+        if pq_.shape != pl_.shape or pq_.dim() != 1:
+            raise ValueError('pair_query and pair_list are two 1-D arrays of one length')
+        out = self._dev.empty((pq_.shape[0], self.M, PQ_KS), torch.float16 if self._lut == 'f16' else torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self._dev.lib.nafp_ivf_pq_adc_tables(_lib.ptr(q), q.shape[0], _lib.ptr(pq_), _lib.ptr(pl_), pq_.shape[0],
+                                                            _lib.ptr(self.centroids), self.nlist, self.d, _lib.ptr(self.pq_centroids),
+                                                            self.M, LUT_CODES[self._lut], _lib.ptr(out), _lib.current_stream()),
+                       'ivf_pq_adc_tables')
+        return out

@@ -6,7 +6,9 @@ fingerprints of one song against the rest); queries = nq random rows with noise 
 copies of eval_faiss.  Measures training time (the index's own seeded training subset), `add` rows/s with the rows already
 on the device, the lazy list build, search time for nq queries (k = 20, nprobe = 40) for the exact index, IVF-Flat
 (nlist 400) and IVF-PQ (nlist 256, M 64, nbits 8) in the same process, and 1-recall@1 / 1-recall@20 of both approximate
-indexes against the exact one (the exact nearest neighbour ranked first / within the top 20).
+indexes against the exact one (the exact nearest neighbour ranked first / within the top 20).  IVF-PQ is searched twice on
+the one trained index, with fp32 ADC tables (`ivfpq_*`, the default) and with binary16 ones (`ivfpq_f16_*`, lut = 'f16'): same
+queries, same process, the two precisions timed alternately.
 
 usage: python tools/ivf_bench.py [N=10000000] [nq=38000] [reps=3]   (one JSON line at the end)"""
 import json
@@ -74,6 +76,27 @@ for name, make in (('ivf', lambda: IVFFlatIndex(d, 400)), ('ivfpq', lambda: IVFP
     nn = Ie[:, :1]
     res[f'{name}_recall_at_1'] = float((Ia[:, :1] == nn).float().mean())
     res[f'{name}_recall_at_20'] = float((Ia == nn).any(1).float().mean())
+    if name == 'ivfpq':                                        # the two table precisions in turn, reps times: the best of each
+        times = {'f32': [res['ivfpq_search_s']], 'f16': []}
+        for lut in ['f16', 'f32'] * reps:
+            idx.lut = lut
+            idx.search_device(q[:256], k)
+            dt, (_, Il) = sync_time(lambda: idx.search_device(q, k))
+            times[lut].append(dt)
+            if lut == 'f16':
+                Ih = Il
+        res['ivfpq_search_s'] = min(times['f32'])
+        res['ivfpq_search_vs_exact'] = res['ivfpq_search_s'] / res['exact_search_s']
+        res['ivfpq_f16_search_s'] = min(times['f16'])
+        res['ivfpq_f16_search_vs_exact'] = res['ivfpq_f16_search_s'] / res['exact_search_s']
+        res['ivfpq_f16_search_vs_f32'] = res['ivfpq_f16_search_s'] / res['ivfpq_search_s']
+        res['ivfpq_search_times_s'] = times
+        res['ivfpq_f16_recall_at_1'] = float((Ih[:, :1] == nn).float().mean())
+        res['ivfpq_f16_recall_at_20'] = float((Ih == nn).any(1).float().mean())
+        res['ivfpq_f16_same_top1_as_f32'] = float((Ih[:, 0] == Ia[:, 0]).float().mean())
+        print(f'ivfpq, fp16 tables: search {res["ivfpq_f16_search_s"]:.3f} s ({res["ivfpq_f16_search_vs_exact"]:.2f} x exact, '
+              f'{res["ivfpq_f16_search_vs_f32"]:.2f} x fp32 tables at {res["ivfpq_search_s"]:.3f} s), 1-recall@1 {res["ivfpq_f16_recall_at_1"]:.4f}, '
+              f'@20 {res["ivfpq_f16_recall_at_20"]:.4f}, top-1 equal to fp32 tables for {res["ivfpq_f16_same_top1_as_f32"]:.4f}', flush=True)
     print(f'{name}: train {res[f"{name}_train_s"]:.2f} s, add {res[f"{name}_add_s"]:.3f} s ({res[f"{name}_add_rows_per_s"] / 1e6:.1f} M rows/s) '
           f'+ lists {res[f"{name}_lists_s"]:.3f} s, search {res[f"{name}_search_s"]:.3f} s ({res[f"{name}_search_vs_exact"]:.2f} x exact), '
           f'1-recall@1 {res[f"{name}_recall_at_1"]:.4f}, @20 {res[f"{name}_recall_at_20"]:.4f}', flush=True)

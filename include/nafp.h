@@ -216,6 +216,32 @@ int nafp_encoder_profile_read(nafp_encoder* enc, int slot, float* ms_out_host);
  * columns} of the last recorded launch.  tools/conv_timeline.py turns the stamps into per-phase times and per-CU overlap. */
 int nafp_conv_timeline(void* dev_buf, int64_t capacity_u64, int cin, int cout, int positions);
 int nafp_conv_timeline_grid(int* out5_host);
+/* Diagnostic, host only (works in a process without a GPU): what the launcher of the GEMM convs will do with conv `layer`
+ * (1 ... 15) of an encoder on (in_f, in_t) features for a launch of `n_seg` segments -- tile, split-K factor and finish, kernel, grid
+ * and its mapping -- under the NAFP_* knobs of this process.  plan_b: the planning batch of the inference forward (0: the launch's own
+ * size, as training); flags: the facts of the call, NAFP_PLAN_* or-ed, the arithmetic (0 f32, 1 bf16x3, 2 bf16x6) in bits 8-9;
+ * slab_floats: the split-K workspace the caller has (0: none).  record_host receives NAFP_CONV_PLAN_FIELDS values:
+ *   [0] kernel (row of the launcher's table; its symbol goes to kernel_name_host, if given) [1] tile rows [2] tile columns
+ *   [3] LDS ring depth [4] dynamic LDS bytes [5-7] grid x, y, z [8] positions and [9] samples per tile [10] sample groups
+ *   [11] position blocks [12] K-steps the split policy counts [13] split-K factor [14] finish: 0 none, 1 finish kernel, 2 in-kernel
+ *   (FULL), 3 in-kernel (PLAIN) [15] float4 per workgroup of the FULL finish kernel [16] grid of the finish kernel [17] kernel mode:
+ *   0 FULL, 1 PLAIN, 2 split-K part [18] epilogue: 0 inference, 1 training, 2 generic statistics, 3 plain / part, 4 / 5 in-kernel
+ *   finish FULL / PLAIN [19] arithmetic [20-22] class order of the positions: kind, size and parity of class 0 [23] option bits
+ *   (1 | 2 wave priority, 4 3-D grid, 8 XCD-aware 1-D grid, 16 ... row-fastest) [24] items per XCD group [25] items in full blocks
+ *   of 8 groups [26] log2 of the column tiles [27] samples per launch when the launch runs as several over sample ranges (grid x
+ *   then follows each range; 0: one launch) [28] ablation bits [29] the workspace (floats) the sizing wants for this layer at n_seg
+ *   (with NAFP_PLAN_SIZE_DGRAD: for its transposed conv as well).
+ * Returns NAFP_ERR_UNSUPPORTED for a shape the launcher refuses ([29] is still set).  tests/test_conv_plan_host.py holds the plans. */
+#define NAFP_CONV_PLAN_FIELDS 30
+#define NAFP_PLAN_PLAIN 1
+#define NAFP_PLAN_DGRAD 2
+#define NAFP_PLAN_V_OUT 4
+#define NAFP_PLAN_TICKETS 8
+#define NAFP_PLAN_SPLIT_WEIGHTS 16
+#define NAFP_PLAN_FUSE0 32
+#define NAFP_PLAN_SIZE_DGRAD 64
+int nafp_conv_plan(int in_f, int in_t, int layer, int64_t n_seg, int64_t plan_b, int flags, int64_t slab_floats,
+                   int64_t* record_host, char* kernel_name_host, int name_capacity);
 
 /* Training (model/trainer.py:41-47: emb = m_fp(feat) under tf.GradientTape, then
  * tape.gradient(loss, m_fp.trainable_variables)).  forward_train is nafp_encoder_forward that

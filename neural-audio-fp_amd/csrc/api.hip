@@ -3,6 +3,7 @@
 #include "nafp_common.h"
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -806,6 +807,28 @@ extern "C" int nafp_conv_timeline(void* dev_buf, int64_t capacity_u64, int cin, 
 extern "C" int nafp_conv_timeline_grid(int* out5_host) {
     if (!out5_host) return NAFP_ERR_INVALID_ARG;
     return conv_timeline_grid(out5_host);
+}
+
+extern "C" int nafp_conv_plan(int in_f, int in_t, int layer, int64_t n_seg, int64_t plan_b, int flags, int64_t slab_floats,
+                              int64_t* record_host, char* kernel_name_host, int name_capacity) {
+    if (in_f <= 0 || in_t <= 0 || layer < 1 || layer > 15 || n_seg <= 0 || plan_b < 0 || slab_floats < 0 || !record_host) return NAFP_ERR_INVALID_ARG;
+    const std::vector<ConvGeom> geom = encoder_geometry(in_f, in_t);
+    ConvPlanIn in{};
+    in.B = n_seg; in.plan_b = plan_b; in.slab_floats = slab_floats;
+    in.plain = flags & NAFP_PLAN_PLAIN; in.dgrad = flags & NAFP_PLAN_DGRAD; in.v_out = flags & NAFP_PLAN_V_OUT; in.tickets = flags & NAFP_PLAN_TICKETS;
+    in.split_weights = flags & NAFP_PLAN_SPLIT_WEIGHTS; in.bf16x3 = (flags >> 8) & 3;
+    in.fuse0 = flags & NAFP_PLAN_FUSE0; in.f0_geom = in.fuse0 ? &geom[0] : nullptr;
+    const ConvPlan pl = plan_conv_gemm(in, geom[layer], conv_knobs());
+    for (int i = 0; i < NAFP_CONV_PLAN_FIELDS; ++i) record_host[i] = 0;
+    record_host[29] = conv_gemm_slab_floats(n_seg, geom[layer], (flags & NAFP_PLAN_SIZE_DGRAD) != 0, plan_b);
+    if (pl.rc != NAFP_OK) return pl.rc;
+    const ConvKernelRow& row = conv_kernel_rows[pl.kernel];
+    const int64_t rec[29] = {pl.kernel, pl.BM, pl.bn, row.ring, pl.lds_bytes, pl.grid.x, pl.grid.y, pl.grid.z, pl.PT, pl.ST, pl.n_sg, pl.n_pb, pl.k_steps,
+                             pl.S, pl.finish, pl.finish_f4, pl.finish_grid, pl.mode, row.epi, row.arith, pl.perm_on, pl.perm_n0, pl.perm_c0,
+                             pl.opt, pl.xcd_group, pl.xcd_full, pl.log2_ncol, pl.range_step, pl.abl};
+    for (int i = 0; i < 29; ++i) record_host[i] = rec[i];
+    if (kernel_name_host && name_capacity > 0) snprintf(kernel_name_host, (size_t)name_capacity, "%s", row.name);
+    return NAFP_OK;
 }
 
 extern "C" int nafp_encoder_div_enc(nafp_encoder* e, const float* flat, int64_t n_seg,

@@ -306,10 +306,10 @@ int launch_conv0_stats(const float* feat, const float* w3, const float* bias, st
 //   instruction count -- K-steps that issue nothing but MFMAs, LDS reads and DMA (skewed across the barrier, body
 //   once per ring slot), an epilogue on sample pairs with v_pk_* arithmetic and straight-line buffer loads/stores
 //   (one instantiation per epilogue kind), geometry once per position slot through LDS.
-//   Env knobs for A/B runs (all read once): NAFP_BM256 (min 128-row tiles for the 256-row tile), NAFP_BN64 /
-//   NAFP_BN64_TILES / NAFP_BN64_MIN (64-column tiles), NAFP_N64S2 (their 2-stage, 5-per-CU kernel), NAFP_SPLITK,
-//   NAFP_SPLIT_INKERNEL (min tiles for the in-kernel split-K finish), NAFP_FWD_PLAN (force tile:split), NAFP_GRID3D,
-//   NAFP_GEMM_PRIO, NAFP_CONV0_ROWS.
+//   What a launch does -- tile, split-K factor and finish, grid mapping, kernel -- is decided in ONE place, plan_conv_gemm()
+//   (conv_plan.hip), from the shape and the env knobs for A/B runs, which are read once into ConvKnobs (nafp_common.h: one line per
+//   knob); launch_conv_gemm below only carries the plan out.  nafp_conv_plan (include/nafp.h) prints the plan of any launch without
+//   a GPU.  (conv0 has a knob of its own, NAFP_CONV0_ROWS.)
 // ============================================================================
 constexpr int BN = 128;          // BM (tile rows) is a template parameter: 128 (4 waves) or 256 (8 waves)
 
@@ -1524,8 +1524,7 @@ __device__ __forceinline__ bool conv_gemm_body(const ConvKernelParams& p) {
     NAFP_GEMM_KERNEL(name_##_infer, BM_, BN_, 16, 3, MINW_, false, 0)                         \
     NAFP_GEMM_KERNEL(name_##_train, BM_, BN_, 16, 3, MINW_, false, 1)                         \
     NAFP_GEMM_KERNEL(name_##_any, BM_, BN_, 16, 3, MINW_, false, 2)                           \
-    NAFP_GEMM_KERNEL(name_##_plain, BM_, BN_, 16, 3, MINW_, false, 3)                         \
-    static void (*const name_##_tab[4])(const ConvKernelParams) = {name_##_infer, name_##_train, name_##_any, name_##_plain};
+    NAFP_GEMM_KERNEL(name_##_plain, BM_, BN_, 16, 3, MINW_, false, 3)
 // BK = 16, 3 stages, 3 workgroups/CU.  The other staging points were built and measured on the MI355X
 // (segments/s at BSZ 640, same run): k16s3 148.2 k | k32s2 (2 WG/CU) 143.6 k | k16s2 (4 WG/CU) 142.7 k |
 // k16s4 (2 WG/CU) 140.9 k | k32s3 (1 WG/CU) 116.4 k; they are not compiled any more.
@@ -1545,39 +1544,26 @@ NAFP_GEMM_KERNEL(conv_gemm_k16s3_plainfin, 128, 128, 16, 3, 3, false, 5)
 NAFP_GEMM_KERNEL(conv_gemm_n64k16s2_infer, 128, 64, 16, 2, 5, false, 0)
 NAFP_GEMM_KERNEL(conv_gemm_n64k16s2_train, 128, 64, 16, 2, 5, false, 1)
 NAFP_GEMM_KERNEL(conv_gemm_n64k16s2_splitfin, 128, 64, 16, 2, 5, false, 4)
-static void (*const conv_gemm_n64k16s2_tab[5])(const ConvKernelParams) = {conv_gemm_n64k16s2_infer, conv_gemm_n64k16s2_train, nullptr, nullptr,
-                                                                           conv_gemm_n64k16s2_splitfin};
-static void (*const conv_gemm_n64k16s3_tab[5])(const ConvKernelParams) = {conv_gemm_n64k16s3_infer, conv_gemm_n64k16s3_train, conv_gemm_n64k16s3_any,
-                                                                           conv_gemm_n64k16s3_plain, conv_gemm_n64k16s3_splitfin};
 // 256 x 128 tile, 8 waves (4 x 2), 72 KB ring -> 2 workgroups = 16 waves per CU (4 per SIMD): the weight tile is staged
 // once per 256 rows instead of once per 128, and a workgroup's fixed costs (geometry, pipeline fill) cover twice the output
 NAFP_GEMM_KERNEL(conv_gemm_m256k16s3_infer, 256, 128, 16, 3, 4, false, 0)
 NAFP_GEMM_KERNEL(conv_gemm_m256k16s3_train, 256, 128, 16, 3, 4, false, 1)
 NAFP_GEMM_KERNEL(conv_gemm_m256k16s3_plain, 256, 128, 16, 3, 4, false, 3)
 // (no generic-statistics instantiation: the launcher takes the 128-row tile when 256 rows are not 4 or 8 samples per position)
-static void (*const conv_gemm_m256k16s3_tab[4])(const ConvKernelParams) = {conv_gemm_m256k16s3_infer, conv_gemm_m256k16s3_train, nullptr,
-                                                                            conv_gemm_m256k16s3_plain};
 
 // experimental split-bf16 products (inference epilogue only), one per tile shape
 NAFP_GEMM_KERNEL_BF16X3(conv_gemm_k16s3_infer_bf16x3, 128, 128, 3, 3)
 NAFP_GEMM_KERNEL_BF16X3(conv_gemm_m256k16s3_infer_bf16x3, 256, 128, 3, 4)
 NAFP_GEMM_KERNEL_BF16X3(conv_gemm_n64k16s2_infer_bf16x3, 128, 64, 2, 5)
-// ... and the exact 3-way split with six products (PREC = 2); the 256-row tile at 2 waves per SIMD (the third plane does not fit 128 VGPRs)
-// (ring depth and occupancy bound of the two large shapes are build-time knobs: tools/build_variant.sh ... -DNAFP_X6_...)
+// ... and the exact 3-way split with six products (PREC = 2), on 128-row tiles only (the third plane does not fit the 256-row tile's 128 VGPRs;
+// the launcher forces 128 rows).  Ring depth and occupancy bound of the 128 x 128 shape are build-time knobs: tools/build_variant.sh ... -DNAFP_X6_...
 #ifndef NAFP_X6_K16_NSTAGE
 #define NAFP_X6_K16_NSTAGE 2                // 2 stages at 138 VGPRs = three workgroups per CU: conv1 0.795 ms against 0.839 with 3 stages (two per CU)
 #endif
 #ifndef NAFP_X6_K16_MINW
 #define NAFP_X6_K16_MINW 3
 #endif
-#ifndef NAFP_X6_M256_NSTAGE
-#define NAFP_X6_M256_NSTAGE 3
-#endif
-#ifndef NAFP_X6_M256_MINW
-#define NAFP_X6_M256_MINW 2
-#endif
 NAFP_GEMM_KERNEL_BF16X6(conv_gemm_k16s3_infer_bf16x6, 128, 128, NAFP_X6_K16_NSTAGE, NAFP_X6_K16_MINW, 0)
-NAFP_GEMM_KERNEL_BF16X6(conv_gemm_m256k16s3_infer_bf16x6, 256, 128, NAFP_X6_M256_NSTAGE, NAFP_X6_M256_MINW, 0)
 NAFP_GEMM_KERNEL_BF16X6(conv_gemm_n64k16s2_infer_bf16x6, 128, 64, 2, 4, 0)
 NAFP_GEMM_KERNEL_BF16X6(conv_gemm_k16s3_plain_bf16x6, 128, 128, NAFP_X6_K16_NSTAGE, NAFP_X6_K16_MINW, 3)      // the split-K parts of the late convs
 // ... with the TRAINING epilogue (forward_train under NAFP_OPT_BF16X3 = 2: the pre-activation is kept for the backward pass)
@@ -1593,10 +1579,44 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_k16s2_fuse0_bf16x6(const Con
     conv_gemm_body<128, 128, 16, 2, true, 0, 2>(p);
 }
 
-// Optional timing events of the launch in flight (ConvGemmArgs::ev_start / ev_stop): they ride on a kernel's own dispatch
-// packet (hipExtLaunchKernel: time stamps of its completion signal), so -- unlike hipEventRecord between two kernels -- they
-// put nothing into the queue and cost the GPU no idle time.
-static thread_local hipEvent_t g_ev_start = nullptr, g_ev_stop = nullptr;
+// Every instantiation the launcher can start, one row each (ConvKernelRow, nafp_common.h): plan_conv_gemm() picks the row by
+// (rows, columns, ring depth, epilogue, arithmetic, fuse0), launch_conv_gemm starts it.  Extra floats per ring stage: the third bf16
+// plane of the weights under the exact split (8 floats per column), for the fused conv0 also that of A (8 per row).
+#define NAFP_ROW(k_, BM_, bn_, ring_, extra_, epi_, arith_, fuse0_) {k_, #k_, BM_, bn_, ring_, extra_, epi_, arith_, fuse0_},
+const ConvKernelRow conv_kernel_rows[] = {
+    NAFP_ROW(conv_gemm_k16s3_infer, 128, 128, 3, 0, 0, 0, false)
+    NAFP_ROW(conv_gemm_k16s3_train, 128, 128, 3, 0, 1, 0, false)
+    NAFP_ROW(conv_gemm_k16s3_any, 128, 128, 3, 0, 2, 0, false)
+    NAFP_ROW(conv_gemm_k16s3_plain, 128, 128, 3, 0, 3, 0, false)
+    NAFP_ROW(conv_gemm_k16s3_plainfin, 128, 128, 3, 0, 5, 0, false)
+    NAFP_ROW(conv_gemm_k16s3_fuse0, 128, 128, 3, 0, 0, 0, true)
+    NAFP_ROW(conv_gemm_n64k16s3_infer, 128, 64, 3, 0, 0, 0, false)
+    NAFP_ROW(conv_gemm_n64k16s3_train, 128, 64, 3, 0, 1, 0, false)
+    NAFP_ROW(conv_gemm_n64k16s3_any, 128, 64, 3, 0, 2, 0, false)
+    NAFP_ROW(conv_gemm_n64k16s3_plain, 128, 64, 3, 0, 3, 0, false)
+    NAFP_ROW(conv_gemm_n64k16s3_splitfin, 128, 64, 3, 0, 4, 0, false)
+    NAFP_ROW(conv_gemm_n64k16s3_plainfin, 128, 64, 3, 0, 5, 0, false)
+    NAFP_ROW(conv_gemm_n64k16s2_infer, 128, 64, 2, 0, 0, 0, false)
+    NAFP_ROW(conv_gemm_n64k16s2_train, 128, 64, 2, 0, 1, 0, false)
+    NAFP_ROW(conv_gemm_n64k16s2_splitfin, 128, 64, 2, 0, 4, 0, false)
+    NAFP_ROW(conv_gemm_m256k16s3_infer, 256, 128, 3, 0, 0, 0, false)
+    NAFP_ROW(conv_gemm_m256k16s3_train, 256, 128, 3, 0, 1, 0, false)
+    NAFP_ROW(conv_gemm_m256k16s3_plain, 256, 128, 3, 0, 3, 0, false)
+    NAFP_ROW(conv_gemm_k16s3_infer_bf16x3, 128, 128, 3, 0, 0, 1, false)
+    NAFP_ROW(conv_gemm_m256k16s3_infer_bf16x3, 256, 128, 3, 0, 0, 1, false)
+    NAFP_ROW(conv_gemm_n64k16s2_infer_bf16x3, 128, 64, 2, 0, 0, 1, false)
+    NAFP_ROW(conv_gemm_k16s3_infer_bf16x6, 128, 128, NAFP_X6_K16_NSTAGE, 128 * 8, 0, 2, false)
+    NAFP_ROW(conv_gemm_k16s3_train_bf16x6, 128, 128, NAFP_X6_K16_NSTAGE, 128 * 8, 1, 2, false)
+    NAFP_ROW(conv_gemm_k16s3_any_bf16x6, 128, 128, NAFP_X6_K16_NSTAGE, 128 * 8, 2, 2, false)
+    NAFP_ROW(conv_gemm_k16s3_plain_bf16x6, 128, 128, NAFP_X6_K16_NSTAGE, 128 * 8, 3, 2, false)
+    NAFP_ROW(conv_gemm_n64k16s2_infer_bf16x6, 128, 64, 2, 64 * 8, 0, 2, false)
+    NAFP_ROW(conv_gemm_n64k16s2_train_bf16x6, 128, 64, 2, 64 * 8, 1, 2, false)
+    NAFP_ROW(conv_gemm_n64k16s2_any_bf16x6, 128, 64, 2, 64 * 8, 2, 2, false)
+    NAFP_ROW(conv_gemm_n64k16s2_plain_bf16x6, 128, 64, 2, 64 * 8, 3, 2, false)
+    NAFP_ROW(conv_gemm_k16s2_fuse0_bf16x6, 128, 128, 2, 128 * 8 + 128 * 8, 0, 2, true)
+};
+#undef NAFP_ROW
+const int conv_kernel_row_count = (int)(sizeof(conv_kernel_rows) / sizeof(conv_kernel_rows[0]));
 
 // The exact 3-way bf16 split of a packed weight tensor (Cout, K), K = 3 Cin a multiple of 16, for the PREC = 2 kernels: x = h + m + l
 // with h = bf16(x), m = bf16(x - h), l = bf16(x - h - m) (each difference is exact in float32; three 8-bit significands hold the 24 bits).
@@ -1647,19 +1667,15 @@ int launch_split_weights_multi(const SplitTable& t, hipStream_t st) {
     return NAFP_OK;
 }
 
-template <typename KernelT>
-static int launch_variant(KernelT kernel, int BM, int BNt, int BK, int NSTAGE, const ConvKernelParams& p, dim3 grid, hipStream_t st,
-                          int extra_stage_floats = 0) {
-    static const int lds_pad = []() { const char* e = getenv("NAFP_LDS_PAD"); return e ? atoi(e) : 0; }();      // diagnostic: extra dynamic LDS per workgroup (changes co-residency)
-    const int lds = (NSTAGE * ((BM + BNt) * BK + extra_stage_floats) + 2 * BM + 96 + (p.f0_feat ? 4 * p.Cin : 0)) * (int)sizeof(float) + lds_pad;
-    NAFP_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    if (g_ev_start || g_ev_stop) {
-        ConvKernelParams pc = p;
-        void* args[] = {(void*)&pc};
-        NAFP_HIP_CHECK(hipExtLaunchKernel((const void*)kernel, grid, dim3(2 * BM), args, (size_t)lds, st, g_ev_start, g_ev_stop, 0));
-        g_ev_start = nullptr; g_ev_stop = nullptr;
+// ev_start / ev_stop (ConvGemmArgs, optional): they ride on the kernel's own dispatch packet (hipExtLaunchKernel: time stamps of its
+// completion signal), so -- unlike hipEventRecord between two kernels -- they put nothing into the queue and cost the GPU no idle time.
+static int launch_variant(const ConvKernelRow& row, int lds, ConvKernelParams p, dim3 grid, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop) {
+    NAFP_HIP_CHECK(hipFuncSetAttribute((const void*)row.fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    if (ev_start || ev_stop) {
+        void* args[] = {(void*)&p};
+        NAFP_HIP_CHECK(hipExtLaunchKernel((const void*)row.fn, grid, dim3(2 * row.BM), args, (size_t)lds, st, ev_start, ev_stop, 0));
     } else {
-        kernel<<<grid, 2 * BM, lds, st>>>(p);
+        row.fn<<<grid, 2 * row.BM, lds, st>>>(p);
     }
     NAFP_LAUNCH_CHECK();
     return NAFP_OK;
@@ -1748,58 +1764,6 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(
     }
 }
 
-// Split-K policy: layers whose M x N tiling yields too few workgroups to fill 256 CUs
-// (the late convs: M = 640...20480 rows at B = 640) split their K-steps across blockIdx.z.
-static int live_k_steps(const ConvGeom& g) {
-    // K-steps (BK = 16) of the taps that read real data for at least one output position
-    const int n_in = g.axis == 0 ? g.Tin : g.Fin, n_out = g.axis == 0 ? g.Tout : g.Fout;
-    int n_live = 0;
-    for (int t = 0; t < 3; ++t) {
-        bool live = false;
-        for (int o = 0; o < n_out && !live; ++o) { const int i = o * g.stride - g.pad + t; live = i >= 0 && i < n_in; }
-        n_live += live;
-    }
-    return n_live * g.Cin / 16;
-}
-
-// 64-column tiles of the FORWARD pass run on the 2-stage ring, 5 workgroups per CU (NAFP_N64S2=0: the 3-stage, 4-per-CU kernel)
-static bool n64_two_stage() {
-    static const bool on = []() { const char* e = getenv("NAFP_N64S2"); return !e || e[0] != '0'; }();
-    return on;
-}
-
-static int choose_split(int64_t n_tiles, int k_steps, int64_t out_floats, double slots = 768.0) {
-    // Score each split factor S by (how full the last round of workgroups is) x (share of a
-    // workgroup's time spent in its K-loop rather than prologue/epilogue); 768 = 256 CUs x 3
-    // resident workgroups.  Splitting costs a slab round trip, so it must win by a margin.
-    static const int force = []() { const char* e = getenv("NAFP_SPLITK"); return e ? atoi(e) : -1; }();
-    if (force == 0) return 1;
-    if (force > 0) return force;
-    if (n_tiles >= 3072) return 1;
-    if (slots == 1280.0)       // forward, 64-column tiles, 5 per CU.  Measured at B = 640: 1280 tiles (convs 6, 8) fill the slots and are
-        // best unsplit; 640 tiles in two parts: conv9 (96 K-steps) 0.187 -> 0.167 ms, conv7 (48 K-steps) 0.098 -> 0.096
-        return (n_tiles >= 1000 || k_steps / 2 < 24 || 2 * out_floats * 4 > ((int64_t)64 << 20)) ? 1 : 2;
-    if (slots == 768.0 && n_tiles <= 200) {
-        // few 128 x 128 tiles (the late convs): measured at B = 640 (tools/plan_sweep.sh) a 3-way split is the best or within
-        // 2 % of it for 80 and 160 tiles, 6-way for 40; keep at least 8 K-steps per part
-        int S = n_tiles <= 40 ? 6 : 3;
-        while (S > 1 && (k_steps / S < 8 || (int64_t)S * out_floats * 4 > ((int64_t)64 << 20))) --S;
-        return S;
-    }
-    const double overhead_steps = 6.0;
-    int best = 1; double best_score = 0.0;
-    for (int S = 1; S <= 16; ++S) {
-        const double k = (double)k_steps / S;
-        if (S > 1 && (k < 8.0 || (int64_t)S * out_floats * 4 > ((int64_t)64 << 20))) break;
-        const double w = (double)n_tiles * S;
-        const double rounds = (double)((int64_t)((w + slots - 1) / slots));
-        double score = (w / (rounds * slots)) * (k / (k + overhead_steps));
-        if (S > 1) score *= 0.93;                      // slab write + read + finish launch
-        if (score > best_score + 1e-9) { best_score = score; best = S; }
-    }
-    return best;
-}
-
 // Split-K finish of a PLAIN launch (transposed conv, G/Hb images): y = sum of the S slabs (+ bias).
 __global__ __launch_bounds__(256) void plain_finish_kernel(const float* __restrict__ slab, int S, const float* __restrict__ bias,
                                                           float* __restrict__ y, int64_t n4, int Cout) {
@@ -1817,175 +1781,6 @@ __global__ __launch_bounds__(256) void plain_finish_kernel(const float* __restri
     }
 }
 
-// K-steps (BK = 16) of a tile of the transposed conv: with stride 2 the parity classes of tile_pos()
-// carry 2 resp. 1 live taps (1.5 on average), with stride 1 all three.  (An estimate for the split-K policy only: the kernel skips
-// dead taps per tile.  [r5] The exact per-class count -- a third of this for the layers whose forward conv has ONE live tap at the
-// 1-s input -- was tried in its place: same-box A/B 11.69 vs 11.75 ms at B = 640, 22.29 vs 22.21 at 1280, 85.6 vs 85.2 at 5120:
-// the split factor is not what limits those launches -- they share the chip with the side stream's weight gradients.)
-static int dgrad_k_steps(const ConvGeom& g) { return (g.stride == 2 ? 3 : 6) * g.Cout / 32; }
-
-static int tile_pt(int P) {
-    int pt = 1;
-    while (pt * 2 <= P && pt * 2 <= 32) pt *= 2;          // largest power of two <= min(P, 32)
-    return pt;
-}
-
-// Position slots of a FORWARD tile.  Default: the largest power of two <= min(P, 32).  Where a sizeable share of the output
-// positions has a tap that reads only zero padding -- TF SAME puts the odd padding element behind the data, so with stride 2
-// that is the LAST output coordinate along the conv axis (tap 2), and for the stride-1 layer on two frames each of the two
-// frames has its own dead tap -- the tile takes positions of ONE class (PT divides both class sizes; along T the classes
-// are made contiguous by tile_pos(), perm 2) and the kernel's tile-wide dead-tap skip drops that tap's K-steps.
-// Taken only when it saves >= 3 % of the launch's MACs and does not cost the launch its register-resident statistics
-// (4 or 8 samples per position).  At the 1-s input and B = 640: conv8 -1/3, conv6 -1/6, conv13 -1/6, convs 4 / 11 -1/12,
-// conv2 -1/24 of their K-steps.  NAFP_TAPCLASS=0 switches it off.
-struct FwdTile { int pt, perm; double saved; };
-static FwdTile fwd_tile(const ConvGeom& g, int BM) {
-    const int P = g.Fout * g.Tout;
-    FwdTile r{tile_pt(P), 0, 0.0};
-    static const int mode = []() { const char* e = getenv("NAFP_TAPCLASS"); return e ? atoi(e) : 1; }();
-    const int L = g.axis == 0 ? g.Tout : g.Fout, n_in = g.axis == 0 ? g.Tin : g.Fin;
-    if (!mode || L < 2) return r;
-    auto mask = [&](int o) { unsigned m = 0; for (int t = 0; t < 3; ++t) { const int i = o * g.stride - g.pad + t; if (i >= 0 && i < n_in) m |= 1u << t; } return m; };
-    unsigned m0 = 0;
-    for (int o = 0; o + 1 < L; ++o) m0 |= mask(o);
-    const unsigned m1 = mask(L - 1);
-    const int n_all = __builtin_popcount(m0 | m1), n0 = __builtin_popcount(m0), n1 = __builtin_popcount(m1);
-    const int64_t c1 = P / L, c0 = (int64_t)c1 * (L - 1);                 // positions per class
-    const double saved = n_all == 0 ? 0.0 : (double)(c0 * (n_all - n0) + c1 * (n_all - n1)) / ((double)P * n_all);
-    if (saved < 0.03) return r;
-    int pt = 1;
-    while (pt * 2 <= 32 && c0 % (pt * 2) == 0 && c1 % (pt * 2) == 0) pt *= 2;
-    const int st = BM / pt, st_def = BM / r.pt;
-    const bool fast = st == 4 || st == 8, fast_def = st_def == 4 || st_def == 8;
-    if (st < 4 || (fast_def && !fast)) return r;
-    r.pt = pt; r.perm = g.axis == 0 ? 2 : 0; r.saved = saved;
-    return r;
-}
-
-// Position slots of a DGRAD tile (rows = input positions of the conv).  With stride 2 the positions are enumerated parity
-// class by parity class (tile_pos(), perm 1: one class receives taps {0, 2}, the other only tap {1}) so that a tile of ONE
-// class skips the structurally zero taps; that needs PT to divide both class sizes.  The default (largest power of two
-// <= min(P, 32)) straddles the classes whenever a class has fewer than 32 positions -- the transposed convs of layers 9,
-// 10, 11, 13, 15 at the 1-s input then multiplied all three taps, twice the needed K-steps (BSZ 5120: dgrad_9 72
-// TFLOP/s of useful work, dgrad_13 59).  Any samples-per-position count works for the PLAIN epilogue.
-static int dgrad_tile_pt(const ConvGeom& g) {
-    const int P = g.Fin * g.Tin;
-    int pt = tile_pt(P);
-    const int L = g.axis == 0 ? g.Tin : g.Fin;
-    if (g.stride == 1 && g.axis == 0 && L == 2 && g.pad == 1) {        // two frames, each with its own dead tap (perm 2)
-        while (pt > 1 && (P / 2) % pt != 0) pt >>= 1;
-        return pt;
-    }
-    if (g.stride != 2 || L < 2) return pt;
-    const int c0 = g.pad & 1, n0 = (L - c0 + 1) / 2;
-    const int per = P / L;                                  // positions per coordinate value along the tap axis
-    const int s0 = per * n0, s1 = per * (L - n0);
-    while (pt > 1 && (s0 % pt != 0 || s1 % pt != 0)) pt >>= 1;
-    return pt;
-}
-
-// Tile height of a launch: 256 rows (8 waves, 2 workgroups per CU) when the launch has enough 128-row tiles to fill the
-// chip several times over with the larger tile as well -- those launches are never split along K; 128 rows otherwise.
-// NAFP_BM256 = minimum number of 128-row tiles (0 = never; default 2000).  Measured at B = 640, same box, ms per launch
-// for convs 1-5 with thresholds 0 / 2000 / 1000: 1.185 0.605 0.316 0.315 0.289 / 1.160 0.591 0.306 0.306 0.293 /
-// 1.166 0.592 0.307 0.306 0.334 -- conv5 has 1280 tiles of 128 rows = 640 of 256: 1.25 rounds of 512 slots.
-static int pick_bm(int64_t B, int P, int Cout) {
-    static const int64_t thr = []() { const char* e = getenv("NAFP_BM256"); return e ? atoll(e) : (int64_t)2000; }();
-    if (thr <= 0) return 128;
-    const int pt = tile_pt(P), ST = 128 / pt;
-    const int64_t n_tiles = ((B + ST - 1) / ST) * ((P + pt - 1) / pt) * (Cout / BN);
-    return n_tiles >= thr ? 256 : 128;
-}
-
-// Tile width of a launch that runs 128-row tiles: 64 columns (4 workgroups per CU, each half the work) where the
-// 128 x 128 tiling gives few, coarse workgroups.  NAFP_BN64: 0 never, 2 whenever Cout allows, 1 (default) by tile count.
-// Diagnostic override for tile-plan sweeps: NAFP_FWD_PLAN="bn:S" forces the column width and split factor of every forward
-// FULL launch on 128-row tiles (where legal); tools/plan_sweep.sh runs the combinations and prints per-conv times.
-struct PlanOverride { int bn, S; };
-static const PlanOverride& plan_override() {
-    static const PlanOverride po = []() {
-        PlanOverride r{0, 0};
-        const char* e = getenv("NAFP_FWD_PLAN");
-        if (e) sscanf(e, "%d:%d", &r.bn, &r.S);
-        return r;
-    }();
-    return po;
-}
-
-// the same for the transposed convs (DGRAD launches on 128-row tiles): NAFP_DGRAD_PLAN="bn:S"
-static const PlanOverride& dgrad_plan_override() {
-    static const PlanOverride po = []() {
-        PlanOverride r{0, 0};
-        const char* e = getenv("NAFP_DGRAD_PLAN");
-        if (e) sscanf(e, "%d:%d", &r.bn, &r.S);
-        return r;
-    }();
-    return po;
-}
-
-static int pick_bn(int64_t n_tiles128, int Cout, int k_steps = 0) {
-    static const int mode = []() { const char* e = getenv("NAFP_BN64"); return e ? atoi(e) : 1; }();
-    static const int64_t thr = []() { const char* e = getenv("NAFP_BN64_TILES"); return e ? atoll(e) : (int64_t)1000; }();
-    if (mode == 0 || Cout % 64 != 0) return 128;
-    if (mode == 2) return 64;
-    // plan sweep at B = 640 (tools/plan_sweep.sh): with <= 160 tiles of 128 x 128 (convs 9-15) the 128-column tile with a
-    // split-K of 3-6 beats the 64-column tile by 8-10 %; with 320-640 tiles (convs 6-8) the 64-column tile wins or ties
-    static const int64_t lo = []() { const char* e = getenv("NAFP_BN64_MIN"); return e ? atoll(e) : (int64_t)200; }();
-    return (n_tiles128 < thr && n_tiles128 >= lo) ? 64 : 128;
-}
-
-// Tile plan of a FORWARD launch (rows x position slots x class order): ONE decision, shared by the launcher and by the
-// workspace sizing below -- the slab is sized for the tile count and split factor of the plan that actually runs.
-struct FwdPlan { int BM, pt, perm; };
-static FwdPlan fwd_plan(int64_t B, const ConvGeom& g, bool full_epilogue, bool fuse0, bool force128 = false) {
-    const int P = g.Fout * g.Tout;
-    FwdPlan r{(fuse0 || force128) ? 128 : pick_bm(B, P, g.Cout), tile_pt(P), 0};
-    if (r.BM == 256 && full_epilogue && 256 / r.pt != 8) r.BM = 128;      // FULL mode on 256 rows keeps its statistics in registers: 8 samples per position
-    if (full_epilogue && !fuse0) {
-        FwdTile ft = fwd_tile(g, r.BM);
-        if (r.BM == 256 && ft.saved == 0.0) {
-            // the 256-row tile cannot hold one class with 8 samples per position (conv8 at large batches: 16 positions
-            // per class), the 128-row tile can: a third of the K-steps outweighs the larger tile's few per cent
-            const FwdTile f2 = fwd_tile(g, 128);
-            if (f2.saved >= 0.10) { r.BM = 128; ft = f2; }
-        }
-        r.pt = ft.pt; r.perm = ft.perm;
-    }
-    return r;
-}
-
-// [r5] The batch size the INFERENCE forward plans for.  Tile shape and split-K factor of a layer used to follow the launch's own
-// batch, so the fp32 summation order of a segment -- the last bits of its fingerprint -- depended on how many segments shared its
-// launch.  nafp_encoder_forward* now plan every launch as if it held fwd_plan_b() segments (640: the bench
-// and generate launch size, so nothing changes there) and only the grid follows B: the bytes of a fingerprint no longer depend on
-// TS_BATCH_SZ or on the launch size.  Training plans per launch as before.
-int64_t fwd_plan_b() {
-    static const int64_t b = []() { const char* e = getenv("NAFP_PLAN_B"); return e ? atoll(e) : (int64_t)640; }();
-    return b;
-}
-
-int64_t conv_gemm_slab_floats(int64_t B, const ConvGeom& g, bool with_dgrad, int64_t plan_b) {
-    const int P = g.Fout * g.Tout;
-    const int64_t Bp = plan_b > 0 ? plan_b : B;
-    const FwdPlan fp = fwd_plan(Bp, g, true, false);
-    const int BM = fp.BM, pt = fp.pt, ST = BM / pt;
-    const int64_t n_tiles = ((Bp + ST - 1) / ST) * ((P + pt - 1) / pt) * (g.Cout / BN);
-    const int bn = BM == 256 ? 128 : pick_bn(n_tiles, g.Cout, live_k_steps(g));
-    int S = BM == 256 ? 1 : choose_split(n_tiles * (BN / bn), live_k_steps(g), Bp * P * g.Cout, bn == 64 ? (n64_two_stage() ? 1280.0 : 1024.0) : 768.0);
-    if (BM == 128 && plan_override().S > 0) S = std::max(S, plan_override().S);
-    int64_t need = S > 1 ? (int64_t)S * B * P * g.Cout : 0;
-    if (with_dgrad && g.Cin % BN == 0 && pick_bm(B, g.Fin * g.Tin, g.Cin) == 128) {
-        const int Pd = g.Fin * g.Tin;
-        const int ptd = dgrad_tile_pt(g), STd = 128 / ptd;
-        const int64_t tiles_d = ((B + STd - 1) / STd) * ((Pd + ptd - 1) / ptd) * (g.Cin / BN);
-        const int bnd = pick_bn(tiles_d, g.Cin);
-        int Sd = choose_split(tiles_d * (BN / bnd), dgrad_k_steps(g), B * Pd * g.Cin, bnd == 64 ? 1024.0 : 768.0);
-        if (dgrad_plan_override().S > 0) Sd = std::max(Sd, dgrad_plan_override().S);
-        if (Sd > 1) need = std::max(need, (int64_t)Sd * B * Pd * g.Cin);
-    }
-    return need;
-}
-
 // Diagnostic (nafp_conv_timeline): the forward GEMM conv of the given shape stamps its phase boundaries into `buf`.
 static struct { unsigned long long* buf; int64_t capacity; int cin, cout, positions; int last_grid[5]; } g_timeline = {};
 int conv_timeline_set(unsigned long long* buf, int64_t capacity_u64, int cin, int cout, int positions) {
@@ -1994,247 +1789,93 @@ int conv_timeline_set(unsigned long long* buf, int64_t capacity_u64, int cin, in
 }
 int conv_timeline_grid(int* out5) { for (int i = 0; i < 5; ++i) out5[i] = g_timeline.last_grid[i]; return NAFP_OK; }
 
+template <int FIN_F4>
+static void launch_splitk_finish(const ConvGemmArgs& a, const ConvPlan& pl, const ConvKernelParams& p, hipStream_t st) {
+    if (a.ev_stop) hipExtLaunchKernelGGL(splitk_finish_kernel<FIN_F4>, dim3(pl.finish_grid), dim3(256), 0, st, nullptr, a.ev_stop, 0, (const float*)a.slab,
+                                         pl.S, a.G, a.Hb, a.gamma_out, a.stats_in, a.stats_out, a.y, a.v_out, p.B, p.P, p.Cout, p.inv_n_in);
+    else splitk_finish_kernel<FIN_F4><<<pl.finish_grid, 256, 0, st>>>(a.slab, pl.S, a.G, a.Hb, a.gamma_out, a.stats_in, a.stats_out, a.y, a.v_out,
+                                                                     p.B, p.P, p.Cout, p.inv_n_in);
+}
+
+// Validate, plan (plan_conv_gemm, conv_plan.hip: every decision), fill the kernel's parameters, launch -- once or per sample range --,
+// then the finish kernel if the plan names one.
 int launch_conv_gemm(const ConvGemmArgs& a, int64_t B, const ConvGeom& g, hipStream_t st) {
-    if (g.Cin % 32 != 0 || g.Cout % BN != 0 || B > (1 << 24)) return NAFP_ERR_UNSUPPORTED;
+    ConvPlanIn in{};
+    in.B = B; in.plan_b = a.plan_b; in.plain = a.plain; in.dgrad = a.dgrad; in.v_out = a.v_out != nullptr; in.tickets = a.tickets != nullptr;
+    in.split_weights = a.wp_hm && a.wp_l; in.bf16x3 = a.bf16x3; in.slab_floats = a.slab ? a.slab_floats : 0;
+    in.fuse0 = a.f0_feat != nullptr; in.f0_geom = a.f0_geom;
+    const ConvPlan pl = plan_conv_gemm(in, g, conv_knobs());
+    if (pl.rc != NAFP_OK) return pl.rc;
+    const ConvKernelRow& row = conv_kernel_rows[pl.kernel];
+    const bool d = a.dgrad, in_kernel = pl.finish == CONV_FINISH_IN_KERNEL_FULL || pl.finish == CONV_FINISH_IN_KERNEL_PLAIN;
+
     ConvKernelParams p;
     p.x = a.x; p.wp = a.wp; p.G = a.G; p.Hb = a.Hb; p.gamma_out = a.gamma_out; p.bias = a.bias;
+    p.wp_hm = row.arith == 2 ? a.wp_hm : nullptr; p.wp_l = row.arith == 2 ? (const unsigned short*)a.wp_l : nullptr;
     p.stats_in = a.stats_in; p.stats_out = a.stats_out; p.y = a.y; p.v_out = a.v_out;
-    p.Fin = g.Fin; p.Tin = g.Tin; p.Cin = g.Cin; p.Tout = g.Tout; p.Cout = g.Cout;
+    // the transposed conv (backward w.r.t. the conv input): rows = input positions, source = dT (B,Fout,Tout,Cout), weights = wp flipped
+    // to (Cin, 3*Cout): the kernel sees the mirrored geometry, see row_geom()
+    p.Fin = d ? g.Fout : g.Fin; p.Tin = d ? g.Tout : g.Tin; p.Cin = d ? g.Cout : g.Cin; p.Tout = d ? g.Tin : g.Tout; p.Cout = d ? g.Cin : g.Cout;
     p.axis = g.axis; p.stride = g.stride; p.pad = g.pad;
-    p.B = (int)B; p.P = g.Fout * g.Tout;
-    // forward launches: fwd_plan() (shared with conv_gemm_slab_floats); the transposed conv picks its rows from ITS output
-    // (plan_b: the inference forward plans as if the launch held plan_b segments -- see fwd_plan_b())
-    const int64_t Bp = (a.plan_b > 0 && !a.plain && !a.dgrad && !a.f0_feat) ? a.plan_b : B;
-    // (the exact-split kernels, bf16x3 == 2, run best on 128-row tiles at three workgroups per CU: measured in profiles/r05_experiments.md)
-    const bool x6 = a.bf16x3 == 2 && !a.plain && !a.dgrad && a.wp_hm && a.wp_l;
-    const bool x6d = a.bf16x3 == 2 && a.plain && a.dgrad && a.wp_hm && a.wp_l;        // a transposed conv on the exact split: 128-row tiles as well
-    const FwdPlan fp = fwd_plan(Bp, g, !a.plain && !a.dgrad, a.f0_feat != nullptr, x6);
-    int BM = a.dgrad ? (x6d ? 128 : pick_bm(B, g.Fin * g.Tin, g.Cin)) : fp.BM;
-    int pt = fp.pt;
-    const int fwd_perm = a.dgrad ? 0 : fp.perm;
-    p.PT = pt; p.ST = BM / pt;
+    p.B = (int)B; p.P = pl.P;
+    p.PT = pl.PT; p.ST = pl.ST;
     p.log2ST = 0;
     while ((1 << p.log2ST) < p.ST) ++p.log2ST;
-    p.n_sg = (int)((B + p.ST - 1) / p.ST);
-    p.sample_in = (int64_t)g.Fin * g.Tin * g.Cin;
-    p.tap_stride = g.axis == 0 ? g.Cin : g.Tin * g.Cin;
-    p.inv_n_in = a.ident_stats ? -1.0 : 1.0 / (double)p.sample_in;
-    p.mode = a.plain ? 1 : 0;
-    p.n_split = 1;
-    p.dgrad = 0; p.perm_on = fwd_perm; p.perm_n0 = 0; p.perm_c0 = 0;
-    int k_steps = live_k_steps(g);
-    if (a.dgrad) {
-        // backward w.r.t. the conv input: rows = input positions, source = dT (B,Fout,Tout,Cout),
-        // weights = wp flipped to (Cin, 3*Cout); see row_geom()
-        if (!a.plain || g.Cout % 32 != 0 || g.Cin % BN != 0 || (g.stride != 1 && g.stride != 2)) return NAFP_ERR_UNSUPPORTED;
-        p.dgrad = 1;
-        p.Fin = g.Fout; p.Tin = g.Tout; p.Cin = g.Cout; p.Cout = g.Cin; p.Tout = g.Tin;
-        p.P = g.Fin * g.Tin;
-        pt = dgrad_tile_pt(g);
-        p.PT = pt; p.ST = BM / pt;
-        p.log2ST = 0;
-        while ((1 << p.log2ST) < p.ST) ++p.log2ST;
-        p.n_sg = (int)((B + p.ST - 1) / p.ST);
-        p.sample_in = (int64_t)g.Fout * g.Tout * g.Cout;
-        const int S = g.axis == 0 ? g.Cout : g.Tout * g.Cout;
-        p.tap_stride = -(S / g.stride);
-        p.inv_n_in = 1.0;
-        const int L = g.axis == 0 ? g.Tin : g.Fin;             // extent of the rows along the tap axis
-        if (g.stride == 2 && L >= 2) {
-            p.perm_on = 1; p.perm_c0 = g.pad & 1;              // class 0: coordinate + pad even -> taps {0, 2}
-            p.perm_n0 = (L - p.perm_c0 + 1) / 2;
-        } else if (g.stride == 1 && g.axis == 0 && L == 2 && g.pad == 1) {
-            // stride 1 on two frames (conv8 at the 1-s input): input frame 0 receives taps {0, 1}, frame 1 taps {1, 2}: the
-            // forward class order (last frame of every line last) separates them
-            p.perm_on = 2;
-        }
-        k_steps = dgrad_k_steps(g);
-    }
-    // per-tile A descriptor covers ST samples: must stay below the 2 GiB OOB marker
-    if ((int64_t)p.ST * p.sample_in * 4 >= ((int64_t)1 << 31)) return NAFP_ERR_UNSUPPORTED;
-    const int64_t wbytes = (int64_t)g.Cout * 3 * g.Cin * 4;
-    if (wbytes >= ((int64_t)1 << 31)) return NAFP_ERR_UNSUPPORTED;
-    p.wp_bytes = (unsigned)wbytes;
-    static const int abl = []() { const char* e = getenv("NAFP_ABL"); return e ? atoi(e) : 0; }();
-    p.abl = a.plain ? 0 : abl;
-    p.tl = nullptr;
-    static const int gemm_prio = []() { const char* e = getenv("NAFP_GEMM_PRIO"); return e ? atoi(e) : 0; }();
-    p.opt = gemm_prio;
-    const int n_pb = (p.P + p.PT - 1) / p.PT;
-    const int64_t n_tiles128 = (int64_t)p.n_sg * n_pb * (p.Cout / BN);
-    const int64_t n_tiles128_plan = ((Bp + p.ST - 1) / p.ST) * n_pb * (p.Cout / BN);      // ... at the planning batch
-    int bn = (BM == 256 || a.f0_feat) ? 128 : pick_bn(n_tiles128_plan, p.Cout, (a.plain || a.dgrad) ? 0 : k_steps);
-    const bool plan_forced = BM == 128 && !a.plain && !a.dgrad && !a.f0_feat && plan_override().bn > 0;
-    if (plan_forced && (plan_override().bn == 128 || p.Cout % 64 == 0)) bn = plan_override().bn;
-    const bool dplan_forced = BM == 128 && a.dgrad && dgrad_plan_override().bn > 0;
-    if (dplan_forced && (dgrad_plan_override().bn == 128 || p.Cout % 64 == 0)) bn = dgrad_plan_override().bn;
-    const int64_t n_tiles = n_tiles128 * (BN / bn);
-    int S = 1;
-    const int64_t out_floats = B * p.P * p.Cout;
-    if (a.slab && !a.f0_feat && BM == 128) {
-        S = choose_split(n_tiles128_plan * (BN / bn), k_steps, Bp * p.P * p.Cout, bn == 64 ? ((n64_two_stage() && !a.plain) ? 1280.0 : 1024.0) : 768.0);
-        if (plan_forced && plan_override().S > 0) { S = plan_override().S; while (S > 1 && k_steps / S < 4) --S; }
-        if (dplan_forced && dgrad_plan_override().S > 0) { S = dgrad_plan_override().S; while (S > 1 && k_steps / S < 4) --S; }
-        if ((int64_t)S * out_floats > a.slab_floats) S = 1;
-        if (x6 && bn == 64 && S == 2 && (p.ST == 4 || p.ST == 8)) S = 1;      // convs 7, 9 at B = 640: unsplit on the bf16 pipe beats the two f32 parts + finish (only where the unsplit launch IS a split-arithmetic one: register-resident statistics)
-    }
-    if (S > 1) { p.mode = a.plain ? 1 : 2; p.n_split = S; p.y = a.slab; p.bias = nullptr; }
-    // FULL split launches on 64-column tiles finish in-kernel (last-arriver) when the caller provides arrival counters
-    // (measured per conv at B = 640: with >= 320 output tiles the last arrivers finish faster than a second launch --
-    // conv7 0.119 -> 0.104 ms, conv9 0.193 -> 0.178 --, with 160 or fewer the finish kernel's finer split wins by 2-8 %)
-    static const int fin_min = []() { const char* e = getenv("NAFP_SPLIT_INKERNEL"); return e ? atoi(e) : 320; }();
-    // (decided at the planning batch like S itself: the two finishes group a sample's statistics into different partial sums)
-    // (round-5 ADVICE: the launch's own tile count used to decide as well -- above ~4096 segments convs 7 and 9 fell back to the finish
-    // kernel and a fingerprint's last bits depended on the launch size again; now a launch with more tiles than arrival counters runs as
-    // several launches over sample ranges, see below)
-    const bool in_kernel_finish = fin_min > 0 && S > 1 && !a.plain && bn == 64 && a.tickets && n_tiles128_plan * (BN / bn) >= fin_min &&
-                                  (int64_t)n_pb * (p.Cout / bn) <= NAFP_TICKET_SLOTS;
-    // PLAIN split launches (the transposed convs) with arrival counters: the last arriver adds the parts and stores the result
-    // (its epilogue is a sum: nothing like the FULL epilogue's serial tail) -- NAFP_PLAIN_INKERNEL=0 restores slab + plain_finish_kernel
-    static const int plain_fin = []() { const char* e = getenv("NAFP_PLAIN_INKERNEL"); return e ? atoi(e) : 1; }();
-    const bool plain_in_kernel = plain_fin > 0 && S > 1 && a.plain && a.tickets && n_tiles <= NAFP_TICKET_SLOTS && !x6d;      // (the exact-split parts finish through plain_finish_kernel)
-    p.tickets = (in_kernel_finish || plain_in_kernel) ? a.tickets : nullptr; p.y_final = a.y;
-    if (plain_in_kernel) p.bias = a.bias;
-    static const int grid3d = []() { const char* e = getenv("NAFP_GRID3D"); return e ? atoi(e) : 1; }();
-    // NAFP_XCDMAP: 0 = the plain 3-D grids, 1 (default) = 1-D grid in XCD-aware order, the operand to keep inside one L2 chosen
-    // by size (column-fastest unless the live weights outweigh the activations read), 2 / 3 = force column- / row-fastest
-    static const int xcdmap = []() { const char* e = getenv("NAFP_XCDMAP"); return e ? atoi(e) : 1; }();
-    const int n_col = p.Cout / bn;
-    p.n_pb = n_pb; p.log2_ncol = 0; p.xcd_group = 1; p.xcd_full = 0;
-    while ((1 << p.log2_ncol) < n_col) ++p.log2_ncol;
-    const int64_t total_wg = (int64_t)p.n_sg * n_pb * n_col * S;
-    // (launches that finish their split-K in-kernel keep the plain grid: measured at B = 640 the map costs convs 7 and 9 5 us each)
-    bool xm = xcdmap != 0 && !a.f0_feat && !in_kernel_finish && !plain_in_kernel && (1 << p.log2_ncol) == n_col && total_wg < ((int64_t)1 << 31);
-    if (xm) {
-        const double a_bytes = (double)B * (double)p.sample_in * 4.0, w_bytes = (double)k_steps * 16.0 * p.Cout * 4.0;
-        const bool row_fast = xcdmap == 3 || (xcdmap == 1 && w_bytes > a_bytes);
-        p.xcd_group = row_fast ? p.n_sg * n_pb : n_col * S;
-        p.xcd_full = (int)(total_wg / (8 * (int64_t)p.xcd_group) * (8 * (int64_t)p.xcd_group));
-        if (p.xcd_group <= 1 || p.xcd_full == 0) xm = false;              // one item per group: the plain order already is this order
-        else p.opt |= row_fast ? (8 | 16) : 8;
-    }
-    const bool g3 = !xm && S == 1 && grid3d != 0 && (grid3d == 1 || BM == 256 || bn == 128);
-    if (g3) p.opt |= 4;
-    const dim3 grid = xm ? dim3((unsigned)total_wg)
-                    : g3 ? dim3((unsigned)p.n_sg, (unsigned)n_pb, (unsigned)(p.Cout / bn))
-                         : dim3((unsigned)((int64_t)p.n_sg * n_pb), (unsigned)(p.Cout / bn), (unsigned)S);
-    if (!xm && (n_pb > 65535 || p.Cout / bn > 65535)) return NAFP_ERR_UNSUPPORTED;
-    // (cin < 0 in nafp_conv_timeline selects the transposed conv -- DGRAD -- of the layer with that |cin|)
-    if (g_timeline.buf && ((!a.plain && !a.dgrad && g.Cin == g_timeline.cin) || (a.dgrad && g.Cin == -g_timeline.cin)) &&
-        g.Cout == g_timeline.cout && g.Fout * g.Tout == g_timeline.positions &&
-        (int64_t)grid.x * grid.y * grid.z * 64 <= g_timeline.capacity) {
-        p.tl = g_timeline.buf;
-        g_timeline.last_grid[0] = (int)grid.x; g_timeline.last_grid[1] = (int)grid.y; g_timeline.last_grid[2] = (int)grid.z;
-        g_timeline.last_grid[3] = BM; g_timeline.last_grid[4] = bn;
-    }
-    int rc;
-    const bool finish_follows = S > 1 && !in_kernel_finish && !plain_in_kernel;
-    g_ev_start = a.ev_start; g_ev_stop = finish_follows ? nullptr : a.ev_stop;
+    p.n_sg = pl.n_sg; p.n_pb = pl.n_pb; p.log2_ncol = pl.log2_ncol; p.xcd_group = pl.xcd_group; p.xcd_full = pl.xcd_full;
+    p.sample_in = (int64_t)p.Fin * p.Tin * p.Cin;
+    p.tap_stride = d ? -((g.axis == 0 ? g.Cout : g.Tout * g.Cout) / g.stride) : (g.axis == 0 ? g.Cin : g.Tin * g.Cin);
+    p.inv_n_in = d ? 1.0 : a.ident_stats ? -1.0 : 1.0 / (double)p.sample_in;
+    p.mode = pl.mode; p.dgrad = d;
+    p.perm_on = pl.perm_on; p.perm_n0 = pl.perm_n0; p.perm_c0 = pl.perm_c0;
+    p.wp_bytes = pl.wp_bytes; p.n_split = pl.S; p.abl = pl.abl; p.opt = pl.opt;
+    // a split launch writes its parts to the slab; the bias is added where the parts meet
+    if (pl.S > 1) { p.y = a.slab; p.bias = pl.finish == CONV_FINISH_IN_KERNEL_PLAIN ? a.bias : nullptr; }
+    p.tickets = in_kernel ? a.tickets : nullptr; p.y_final = a.y;
     p.f0_feat = nullptr; p.f0_w = nullptr; p.f0_bias = nullptr; p.f0_gamma = nullptr;
     p.f0_T = 0; p.f0_stride = 1; p.f0_pad = 0; p.f0_gstat = nullptr; p.f0_group = 0; p.f0_segnorm = 0;
-    p.sj = (a.sj && a.plain) ? *a.sj : ScalarsJob{nullptr, nullptr, nullptr, nullptr, 0, 0.0};
     if (a.f0_feat) {
-        // conv0 generated in-kernel: this conv must be the 3x1 conv that consumes conv0's output
-        if (a.plain || S != 1 || !a.f0_geom || g.axis != 1 || a.f0_geom->Cout != g.Cin || a.f0_geom->Tout != g.Tin ||
-            a.f0_geom->Fin != g.Fin || g.Cin % 16 != 0)
-            return NAFP_ERR_UNSUPPORTED;
         p.f0_feat = a.f0_feat; p.f0_w = a.f0_w; p.f0_bias = a.f0_bias; p.f0_gamma = a.f0_gamma;
         p.f0_T = a.f0_geom->Tin; p.f0_stride = a.f0_geom->stride; p.f0_pad = a.f0_geom->pad;
-        if (a.v_out || (p.ST != 4 && p.ST != 8)) return NAFP_ERR_UNSUPPORTED;          // the fused kernel carries the inference epilogue only
         p.f0_gstat = a.f0_gstat; p.f0_group = a.f0_group; p.f0_segnorm = a.f0_segnorm;
-        if (a.bf16x3 == 2 && a.wp_hm && a.wp_l) {
-            if (g.Cin != 128) return NAFP_ERR_UNSUPPORTED;          // the exact-split generator is written for conv0's 128 channels
-            p.wp_hm = a.wp_hm; p.wp_l = (const unsigned short*)a.wp_l;
-            return launch_variant(conv_gemm_k16s2_fuse0_bf16x6, 128, 128, 16, 2, p, grid, st, 128 * 8 + 128 * 8);      // + A's third plane, + the weights' third plane
-        }
-        return launch_variant(conv_gemm_k16s3_fuse0, 128, 128, 16, 3, p, grid, st);
     }
-    const bool fast_st = p.ST == 4 || p.ST == 8;
-    if (plain_in_kernel)
-        return bn == 64 ? launch_variant(conv_gemm_n64k16s3_plainfin, 128, 64, 16, 3, p, grid, st)
-                        : launch_variant(conv_gemm_k16s3_plainfin, 128, 128, 16, 3, p, grid, st);
-    const int epi = in_kernel_finish ? 4 : p.mode != 0 ? 3 : (!fast_st ? 2 : (p.v_out ? 1 : 0));
-    const bool two_stage = n64_two_stage() && bn == 64 && (epi == 0 || epi == 1 || epi == 4);
-    if (a.bf16x3 == 2 && epi == 0 && (bn == 128 || two_stage) && a.wp_hm && a.wp_l) {
-        p.wp_hm = a.wp_hm; p.wp_l = (const unsigned short*)a.wp_l;
-        return BM == 256 ? launch_variant(conv_gemm_m256k16s3_infer_bf16x6, 256, 128, 16, NAFP_X6_M256_NSTAGE, p, grid, st, 128 * 8)
-             : bn == 64 ? launch_variant(conv_gemm_n64k16s2_infer_bf16x6, 128, 64, 16, 2, p, grid, st, 64 * 8)
-                        : launch_variant(conv_gemm_k16s3_infer_bf16x6, 128, 128, 16, NAFP_X6_K16_NSTAGE, p, grid, st, 128 * 8);
+    p.sj = (a.sj && a.plain) ? *a.sj : ScalarsJob{nullptr, nullptr, nullptr, nullptr, 0, 0.0};
+    // (cin < 0 in nafp_conv_timeline selects the transposed conv -- DGRAD -- of the layer with that |cin|)
+    p.tl = nullptr;
+    if (g_timeline.buf && ((!a.plain && !a.dgrad && g.Cin == g_timeline.cin) || (a.dgrad && g.Cin == -g_timeline.cin)) &&
+        g.Cout == g_timeline.cout && g.Fout * g.Tout == g_timeline.positions &&
+        (int64_t)pl.grid.x * pl.grid.y * pl.grid.z * 64 <= g_timeline.capacity) {
+        p.tl = g_timeline.buf;
+        g_timeline.last_grid[0] = (int)pl.grid.x; g_timeline.last_grid[1] = (int)pl.grid.y; g_timeline.last_grid[2] = (int)pl.grid.z;
+        g_timeline.last_grid[3] = pl.BM; g_timeline.last_grid[4] = pl.bn;
     }
-    // the training epilogue on the exact split (x6 forces 128-row tiles), and the generic-statistics epilogue (samples per position other
-    // than 4 / 8: the small late layers of a large training batch); launches that need the in-kernel-finish epilogue stay on the f32 kernels
-    static const bool x6_any = []() { const char* e = getenv("NAFP_X6_ANY"); return !e || e[0] != '0'; }();      // (A/B knob)
-    if (x6 && epi == 2 && BM == 128 && x6_any) {
-        p.wp_hm = a.wp_hm; p.wp_l = (const unsigned short*)a.wp_l;
-        return bn == 64 ? launch_variant(conv_gemm_n64k16s2_any_bf16x6, 128, 64, 16, 2, p, grid, st, 64 * 8)
-                        : launch_variant(conv_gemm_k16s3_any_bf16x6, 128, 128, 16, NAFP_X6_K16_NSTAGE, p, grid, st, 128 * 8);
-    }
-    if (x6 && epi == 1 && BM == 128 && (bn == 128 || two_stage)) {
-        p.wp_hm = a.wp_hm; p.wp_l = (const unsigned short*)a.wp_l;
-        return bn == 64 ? launch_variant(conv_gemm_n64k16s2_train_bf16x6, 128, 64, 16, 2, p, grid, st, 64 * 8)
-                        : launch_variant(conv_gemm_k16s3_train_bf16x6, 128, 128, 16, NAFP_X6_K16_NSTAGE, p, grid, st, 128 * 8);
-    }
-    if (a.bf16x3 && epi == 0 && (bn == 128 || two_stage))
-        return BM == 256 ? launch_variant(conv_gemm_m256k16s3_infer_bf16x3, 256, 128, 16, 3, p, grid, st)
-             : bn == 64 ? launch_variant(conv_gemm_n64k16s2_infer_bf16x3, 128, 64, 16, 2, p, grid, st)
-                        : launch_variant(conv_gemm_k16s3_infer_bf16x3, 128, 128, 16, 3, p, grid, st);
-    if (x6 && epi == 3 && bn == 128 && BM == 128 && p.mode == 2) {
-        p.wp_hm = a.wp_hm; p.wp_l = (const unsigned short*)a.wp_l;
-        rc = launch_variant(conv_gemm_k16s3_plain_bf16x6, 128, 128, 16, NAFP_X6_K16_NSTAGE, p, grid, st, 128 * 8);
-    } else if (x6d && epi == 3 && BM == 128) {
-        p.wp_hm = a.wp_hm; p.wp_l = (const unsigned short*)a.wp_l;
-        rc = bn == 64 ? launch_variant(conv_gemm_n64k16s2_plain_bf16x6, 128, 64, 16, 2, p, grid, st, 64 * 8)
-                      : launch_variant(conv_gemm_k16s3_plain_bf16x6, 128, 128, 16, NAFP_X6_K16_NSTAGE, p, grid, st, 128 * 8);
-    } else if (in_kernel_finish && n_tiles > NAFP_TICKET_SLOTS) {
-        // more output tiles than arrival counters: sample ranges of at most NAFP_TICKET_SLOTS tiles, one launch each (the last arrivers
-        // leave the counters at zero, so the ranges reuse them and the slab in stream order); every sample sees exactly the launch it
-        // would have seen in a smaller batch
-        const int64_t tiles_per_sg = (int64_t)n_pb * (p.Cout / bn);
-        const int64_t sg_per_launch = NAFP_TICKET_SLOTS / tiles_per_sg;
-        const int64_t b_step = sg_per_launch * p.ST;
+
+    const bool finish_follows = pl.finish == CONV_FINISH_KERNEL;
+    hipEvent_t ev_stop = finish_follows ? nullptr : a.ev_stop;
+    if (pl.range_step > 0) {
+        // sample ranges, one launch each (ConvPlan::range_step)
         const int64_t out_per_sample = (int64_t)p.P * p.Cout;
-        hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;
-        rc = NAFP_OK;
-        for (int64_t b0 = 0; b0 < B && rc == NAFP_OK; b0 += b_step) {
+        int rc = NAFP_OK;
+        for (int64_t b0 = 0; b0 < B && rc == NAFP_OK; b0 += pl.range_step) {
             ConvKernelParams q = p;
-            const int64_t bc = std::min<int64_t>(b_step, B - b0);
+            const int64_t bc = std::min<int64_t>(pl.range_step, B - b0);
             q.B = (int)bc; q.n_sg = (int)((bc + p.ST - 1) / p.ST);
             q.x = p.x + b0 * p.sample_in; q.y_final = p.y_final + b0 * out_per_sample;
             if (p.v_out) q.v_out = p.v_out + b0 * out_per_sample;
             q.stats_in = p.stats_in + 2 * b0; q.stats_out = p.stats_out + 2 * b0;
-            g_ev_start = b0 == 0 ? ev0 : nullptr; g_ev_stop = b0 + b_step >= B ? ev1 : nullptr;
-            const dim3 gq((unsigned)((int64_t)q.n_sg * n_pb), (unsigned)(p.Cout / bn), (unsigned)S);
-            rc = two_stage ? launch_variant(conv_gemm_n64k16s2_tab[epi], 128, 64, 16, 2, q, gq, st)
-                           : launch_variant(conv_gemm_n64k16s3_tab[epi], 128, 64, 16, 3, q, gq, st);
+            rc = launch_variant(row, pl.lds_bytes, q, dim3((unsigned)((int64_t)q.n_sg * pl.n_pb), pl.grid.y, pl.grid.z), st,
+                                b0 == 0 ? a.ev_start : nullptr, b0 + pl.range_step >= B ? ev_stop : nullptr);
         }
         return rc;
-    } else
-    rc = BM == 256 ? launch_variant(conv_gemm_m256k16s3_tab[epi], 256, 128, 16, 3, p, grid, st)
-         : (bn == 64 && two_stage) ? launch_variant(conv_gemm_n64k16s2_tab[epi], 128, 64, 16, 2, p, grid, st)
-         : bn == 64 ? launch_variant(conv_gemm_n64k16s3_tab[epi], 128, 64, 16, 3, p, grid, st)
-                    : launch_variant(conv_gemm_k16s3_tab[epi], 128, 128, 16, 3, p, grid, st);
-    if (rc != NAFP_OK || S == 1 || in_kernel_finish) return rc;
-    if (a.plain) {
-        const int64_t n4 = out_floats / 4;
-        const dim3 fgrid((unsigned)std::min<int64_t>((n4 + 255) / 256, 8192));
-        if (a.ev_stop) hipExtLaunchKernelGGL(plain_finish_kernel, fgrid, dim3(256), 0, st, nullptr, a.ev_stop, 0, (const float*)a.slab, S, a.bias, a.y, n4, p.Cout);
-        else plain_finish_kernel<<<fgrid, 256, 0, st>>>(a.slab, S, a.bias, a.y, n4, p.Cout);
-        NAFP_LAUNCH_CHECK();
-        return NAFP_OK;
     }
-    if (4096 / g.Cout + 1 > FIN_MAXS || g.Cout < 128) return NAFP_ERR_UNSUPPORTED;      // a wave (256 floats) spans <= 2 rows
-    const int64_t f4 = out_floats / 4;
-    const int64_t f4_plan = Bp * p.P * p.Cout / 4;          // the finish kernel's block size follows the planning batch (it sets the partial sums of the statistics)
-#define NAFP_FIN(E_)                                                                                             \
-    if (a.ev_stop) hipExtLaunchKernelGGL(splitk_finish_kernel<E_>, dim3((unsigned)((f4 + (E_) - 1) / (E_))), dim3(256), 0, st, nullptr,   \
-                                         a.ev_stop, 0, (const float*)a.slab, S, a.G, a.Hb, a.gamma_out, a.stats_in, a.stats_out, a.y,   \
-                                         a.v_out, p.B, p.P, g.Cout, p.inv_n_in);                                   \
-    else splitk_finish_kernel<E_><<<dim3((unsigned)((f4 + (E_) - 1) / (E_))), 256, 0, st>>>(                       \
-        a.slab, S, a.G, a.Hb, a.gamma_out, a.stats_in, a.stats_out, a.y, a.v_out, p.B, p.P, g.Cout, p.inv_n_in)
-    if (f4_plan >= 1024 * 1024) { NAFP_FIN(1024); }
-    else if (f4_plan >= 1024 * 512) { NAFP_FIN(512); }
-    else { NAFP_FIN(256); }
-#undef NAFP_FIN
+    const int rc = launch_variant(row, pl.lds_bytes, p, pl.grid, st, a.ev_start, ev_stop);
+    if (rc != NAFP_OK || !finish_follows) return rc;
+    if (a.plain) {
+        const int64_t n4 = B * p.P * p.Cout / 4;
+        if (a.ev_stop) hipExtLaunchKernelGGL(plain_finish_kernel, dim3(pl.finish_grid), dim3(256), 0, st, nullptr, a.ev_stop, 0, (const float*)a.slab, pl.S, a.bias, a.y, n4, p.Cout);
+        else plain_finish_kernel<<<pl.finish_grid, 256, 0, st>>>(a.slab, pl.S, a.bias, a.y, n4, p.Cout);
+    } else if (pl.finish_f4 == 1024) launch_splitk_finish<1024>(a, pl, p, st);
+    else if (pl.finish_f4 == 512) launch_splitk_finish<512>(a, pl, p, st);
+    else launch_splitk_finish<256>(a, pl, p, st);
     NAFP_LAUNCH_CHECK();
     return NAFP_OK;
 }

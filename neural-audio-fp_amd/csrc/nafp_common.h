@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
 #include <vector>
 
 #include "../../include/nafp.h"
@@ -197,6 +199,82 @@ int launch_conv0_stats(const float* feat, const float* w3, const float* bias, st
 int64_t conv_gemm_slab_floats(int64_t B, const ConvGeom& g, bool with_dgrad = false, int64_t plan_b = 0);   // workspace the split-K policy wants
 int64_t fwd_plan_b();      // the batch size the inference forward plans its tiles for (NAFP_PLAN_B, default 640; 0 = the launch's own size)
 int launch_conv_gemm(const ConvGemmArgs& a, int64_t B, const ConvGeom& g, hipStream_t st);
+
+// ---- the plan of a conv GEMM launch (conv_plan.hip: host only) -----------------------------------------------------------------
+// Everything launch_conv_gemm decides, as a value: plan_conv_gemm() computes it from the shape, the facts of ConvGemmArgs that matter
+// and the knobs; it calls no HIP function and reads no global state.  launch_conv_gemm fills ConvKernelParams from it,
+// conv_gemm_slab_floats sizes the workspace with it, nafp_conv_plan (include/nafp.h) prints it, tests/test_conv_plan_host.py holds it.
+
+// The environment knobs of the launcher and of the sizing, for A/B runs (tools/plan_sweep.sh, dgrad_plan_sweep.sh, abl_*): ALL of them, name,
+// production default and meaning.  A ConvKnobs object reads the environment where it is made; the launcher and the sizing use conv_knobs(),
+// made once per process.
+inline int64_t env_int(const char* name, int64_t dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; }
+inline bool env_on(const char* name) { const char* e = getenv(name); return !e || e[0] != '0'; }
+struct PlanOverride { int bn = 0, S = 0; };      // "bn:S"
+inline PlanOverride env_plan(const char* name) { PlanOverride r; const char* e = getenv(name); if (e) sscanf(e, "%d:%d", &r.bn, &r.S); return r; }
+struct ConvKnobs {
+    int64_t bm256_min_tiles = env_int("NAFP_BM256", 2000);      // least number of 128-row tiles for the 256-row tile (0 = never), see pick_bm()
+    int bn64 = (int)env_int("NAFP_BN64", 1);                    // 64-column tiles: 0 never, 2 whenever Cout allows, 1 by tile count ...
+    int64_t bn64_tiles = env_int("NAFP_BN64_TILES", 1000);      // ... below this many 128 x 128 tiles
+    int64_t bn64_min = env_int("NAFP_BN64_MIN", 200);           // ... and from this many on, see pick_bn()
+    bool n64_two_stage = env_on("NAFP_N64S2");                  // forward 64-column tiles on the 2-stage ring, 5 workgroups per CU (0: 3 stages, 4 per CU)
+    int splitk = (int)env_int("NAFP_SPLITK", -1);               // 0 never split along K, n > 0 always n-way, -1 by choose_split()
+    int split_inkernel = (int)env_int("NAFP_SPLIT_INKERNEL", 320);   // least number of 64-column tiles for the in-kernel finish of a FULL split (0 = never)
+    int plain_inkernel = (int)env_int("NAFP_PLAIN_INKERNEL", 1);     // 0 = PLAIN split launches finish through slab + plain_finish_kernel
+    PlanOverride fwd_plan = env_plan("NAFP_FWD_PLAN");          // forces column width and split factor of every forward FULL launch on 128-row tiles (where legal)
+    PlanOverride dgrad_plan = env_plan("NAFP_DGRAD_PLAN");      // the same for the transposed convs
+    int tapclass = (int)env_int("NAFP_TAPCLASS", 1);            // 0 = forward tiles never take the positions of one tap class, see fwd_tile()
+    int64_t plan_b = env_int("NAFP_PLAN_B", 640);               // the batch size the inference forward plans for, see fwd_plan_b()
+    int grid3d = (int)env_int("NAFP_GRID3D", 1);                // 3-D grid of the unsplit launches off the XCD map: 0 never, 1 always, 2 only 256-row or 128-column tiles
+    int xcdmap = (int)env_int("NAFP_XCDMAP", 1);                // 0 = plain grids, 1 = 1-D grid in XCD-aware order (operand kept in one L2 chosen by size), 2 / 3 = force column- / row-fastest
+    int gemm_prio = (int)env_int("NAFP_GEMM_PRIO", 0);          // bit 0 / 1 = geometry prologue / epilogue at raised wave priority (ConvKernelParams::opt)
+    bool x6_any = env_on("NAFP_X6_ANY");                        // 0 = the generic-statistics epilogue stays on the f32 kernels under the exact split
+    int abl = (int)env_int("NAFP_ABL", 0);                      // ablation bits of a -DNAFP_ABLATION build (FULL launches only)
+    int lds_pad = (int)env_int("NAFP_LDS_PAD", 0);              // extra dynamic LDS bytes per workgroup (diagnostic: changes co-residency)
+};
+const ConvKnobs& conv_knobs();
+
+// One row per instantiation of conv_gemm_body that the launcher can start (the table itself: conv.hip, behind the kernels)
+struct ConvKernelParams;
+struct ConvKernelRow {
+    void (*fn)(const ConvKernelParams);
+    const char* name;                 // the kernel's symbol
+    int BM, bn, ring;                 // tile rows / columns, depth of the LDS ring
+    int extra_stage_floats;           // per ring stage, beyond (BM + bn) * 16: the third bf16 planes of the exact split
+    int epi;                          // 0 inference, 1 training (keeps the pre-activation), 2 generic statistics, 3 PLAIN / split-K part, 4 FULL split finished in-kernel, 5 PLAIN split finished in-kernel
+    int arith;                        // 0 f32, 1 bf16x3, 2 bf16x6 (exact 3-way split)
+    bool fuse0;                       // conv0 generated in-kernel
+};
+extern const ConvKernelRow conv_kernel_rows[];
+extern const int conv_kernel_row_count;
+
+enum ConvFinish { CONV_FINISH_NONE = 0, CONV_FINISH_KERNEL = 1, CONV_FINISH_IN_KERNEL_FULL = 2, CONV_FINISH_IN_KERNEL_PLAIN = 3 };
+struct ConvPlanIn {
+    int64_t B, plan_b;                // samples of the launch; ConvGemmArgs::plan_b
+    bool plain, dgrad, v_out, tickets, split_weights;      // v_out / tickets / (wp_hm and wp_l) given
+    int bf16x3;
+    int64_t slab_floats;              // 0: no slab
+    bool fuse0; const ConvGeom* f0_geom;
+    bool sizing;                      // conv_gemm_slab_floats asks, see there
+};
+struct ConvPlan {
+    int rc;                           // NAFP_OK, or NAFP_ERR_UNSUPPORTED: nothing else is valid then
+    int kernel;                       // row of conv_kernel_rows
+    int BM, bn, PT, ST;               // tile = BM rows (PT positions x ST samples) x bn columns
+    int P, n_sg, n_pb;                // rows per sample; sample groups and position blocks of the launch
+    int perm_on, perm_n0, perm_c0;    // class order of the positions (tile_pos())
+    int k_steps;                      // K-steps the split-K policy counts
+    int S;                            // split-K factor
+    int finish;                       // ConvFinish
+    int finish_f4; unsigned finish_grid;   // CONV_FINISH_KERNEL: float4 per workgroup (FULL: splitk_finish_kernel<finish_f4>; PLAIN: 0, plain_finish_kernel) and its grid
+    int mode;                         // ConvKernelParams::mode: 0 FULL, 1 PLAIN, 2 split-K part of a FULL launch
+    int lds_bytes;                    // dynamic LDS of the kernel
+    dim3 grid;                        // of the whole launch (a launch cut into ranges: y and z hold, x follows the range's sample groups)
+    int opt, xcd_group, xcd_full, log2_ncol;
+    int64_t range_step;               // > 0: the launch runs as several, over sample ranges of this many samples
+    int abl; unsigned wp_bytes;       // ConvKernelParams::abl (the NAFP_ABL knob), ::wp_bytes (checked against the buffer descriptor's 2 GiB)
+};
+ConvPlan plan_conv_gemm(const ConvPlanIn& in, const ConvGeom& g, const ConvKnobs& k);
 int conv_timeline_set(unsigned long long* buf, int64_t capacity_u64, int cin, int cout, int positions);
 int conv_timeline_grid(int* out5);
 

@@ -4,7 +4,8 @@ boundaries (nafp_conv_timeline), this script turns the stamps into
   * per CU: the share of the launch during which 0, 1, 2, 3 ... workgroups are inside their K-loop, and the gap between
     one workgroup leaving a CU slot and the next one's first K-step.
 
-    python tools/conv_timeline.py [conv_index=1] [batch=640]
+    python tools/conv_timeline.py [conv_index=1] [batch=640] [dgrad]
+    python tools/conv_timeline.py plan [batch=640]        # only print what the launcher will do with each conv (no GPU needed)
 """
 import ctypes
 import os
@@ -37,7 +38,23 @@ def geometry(j, F=256, T=32):
         cin = CH[k]
 
 
+def print_plan(lib, j, B, dgrad=False):
+    """The launcher's plan for conv j (nafp_conv_plan, include/nafp.h): inference at the planning batch, or the transposed conv."""
+    rec, name = (ctypes.c_int64 * 30)(), ctypes.create_string_buffer(96)
+    flags, plan_b = (1 | 2 | 8 | 64, 0) if dgrad else (8, 640)
+    lib.nafp_conv_plan(256, 32, j, B, plan_b, flags, 0, rec, None, 0)
+    slab = rec[29]                                                # the workspace the sizing wants for this layer (the call sites give at least that)
+    rc = lib.nafp_conv_plan(256, 32, j, B, plan_b, flags, slab, rec, name, len(name))
+    r = list(rec)
+    print(f'conv {j}{" dgrad" if dgrad else ""} B {B}: rc {rc}  {name.value.decode()}  tile {r[1]} x {r[2]} ({r[8]} positions x {r[9]} samples)  '
+          f'grid {r[5]} x {r[6]} x {r[7]}  split-K {r[13]} finish {r[14]}  K-steps {r[12]}  LDS {r[4]} B  opt {r[23]}  range step {r[27]}')
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == 'plan':
+        for j in range(1, 16):
+            print_plan(_lib.load(), j, int(sys.argv[2]) if len(sys.argv) > 2 else 640)
+        return
     j = int(sys.argv[1]) if len(sys.argv) > 1 else 1
     B = int(sys.argv[2]) if len(sys.argv) > 2 else 640
     dgrad = len(sys.argv) > 3 and sys.argv[3] == 'dgrad'          # the transposed conv of layer j in a train step
@@ -50,6 +67,7 @@ def main():
         emb = fp(pre(x, group_size=B))
     torch.cuda.synchronize()
     cin, cout, pos = geometry(j)
+    print_plan(lib, j, B, dgrad)
     cap = 1 << 24
     buf = torch.zeros(cap, dtype=torch.int64, device='cuda')
     rc = lib.nafp_conv_timeline(ctypes.c_void_p(buf.data_ptr()), cap, -cin if dgrad else cin, cout, pos)

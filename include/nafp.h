@@ -500,7 +500,7 @@ int nafp_search_seq_scores(const float* query, const float* index, int64_t n_ind
  * Ties everywhere: the smaller id (list, code, row) first.  All pointers are device pointers; results
  * are bit-identical from run to run and do not depend on how rows or queries are batched.
  * Status: NAFP_ERR_INVALID_ARG for a null pointer or a negative size, NAFP_ERR_UNSUPPORTED for a dim
- * outside 64 / 128 / 256, k > 32, nprobe > 128, M != 64, n_buckets / nlist > 16384 or an unknown lut;
+ * outside 64 / 128 / 256, k > 32 (k1 > 128 for the wide first stage of IVFPQ-RR), nprobe > 128, M != 64, n_buckets / nlist > 16384 or an unknown lut;
  * checked before any GPU call.  The *_workspace_bytes queries return -1 for such arguments.
  * ------------------------------------------------------------------------------------------- */
 
@@ -582,6 +582,47 @@ int nafp_ivf_pq_search_ex(const float* query, int64_t n_query, const float* cent
 int nafp_ivf_pq_adc_tables(const float* query, int64_t n_query, const int32_t* pair_query,
                            const int32_t* pair_list, int64_t n_pairs, const float* centroids, int nlist, int dim,
                            const float* pq_centroids, int M, int lut, void* out, void* stream);
+
+/* IVFPQ-RR (faiss IndexIVFPQR as eval/utils/get_index_faiss.py builds it: IVF-PQ plus a refine product
+ * quantizer of M_refine = 4 sub-spaces x 2^4 codewords on the PQ stage's own residuals, and a re-ranking of
+ * k * k_factor first-stage candidates by the distance to the refined reconstruction).  refine_centroids
+ * (4, 16, dim / 4) float32; refine codes 2 bytes per row in insertion order, byte0 = c0 | c1 << 4, byte1 =
+ * c2 | c3 << 4.  Other M_refine / nbits_refine: NAFP_ERR_UNSUPPORTED. */
+
+/* out (n, dim) = x - decode(codes): x minus the PQ codewords its codes (n, M) name.  n * dim < 2^32 (one launch);
+ * more rows: NAFP_ERR_UNSUPPORTED, call it in pieces. */
+int nafp_ivf_pq_residuals(const float* x, int64_t n, int dim, const float* pq_centroids, int M, const uint8_t* codes,
+                          float* out, void* stream);
+/* per row of x (n, dim) and refine sub-space the nearest of the 16 codewords (equal distances: the smaller
+ * code).  packed 1: codes (n, 2) as above; packed 0: codes (n, 4), one code per byte (bucketing keys). */
+int nafp_ivf_refine_encode(const float* x, int64_t n, int dim, const float* refine_centroids, int M_refine,
+                           int nbits_refine, int packed, uint8_t* codes, void* stream);
+
+/* The wide first stage: nafp_ivf_pq_search_ex's contract (tables, distances, order, padding) for k1 <= 128
+ * results per query.  nafp_ivf_pq_search[_ex] itself keeps refusing k > 32.  Workspace of this call and of
+ * nafp_ivf_pqr_search (with k1 = k * k_factor): nafp_ivf_pq_wide_workspace_bytes; -1 for k1 > 128. */
+int64_t nafp_ivf_pq_wide_workspace_bytes(int64_t n_query, int nlist, int nprobe, int k1);
+int nafp_ivf_pq_search_wide(const float* query, int64_t n_query, const float* centroids, int nlist, int dim,
+                            int nprobe, const float* pq_centroids, int M, const uint8_t* codes_sorted,
+                            const int32_t* offsets, const int32_t* ids, int k1, float* out_dist, int32_t* out_ids,
+                            int lut, void* workspace, int64_t workspace_bytes, void* stream);
+/* The re-rank: for each of the k1 <= 128 candidate rows cand_ids (n_query, k1) names (-1: none), dist = sum over
+ * dd ascending of (q[dd] - ((centroids[assign[id]][dd] + P[m][code_m][u]) + R[mr][rcode_mr][u']))^2 in fp32;
+ * out (n_query, k), k <= 32 and <= k1: the k smallest by (distance, id), padded with +inf / -1.  assign (n_rows),
+ * codes (n_rows, M) and refine_codes (n_rows, 2) are in insertion order. */
+int nafp_ivf_pqr_rerank(const float* query, int64_t n_query, int dim, const int32_t* cand_ids, int k1,
+                        const float* centroids, const int32_t* assign, const float* pq_centroids, int M,
+                        const uint8_t* codes, const float* refine_centroids, int M_refine, int nbits_refine,
+                        const uint8_t* refine_codes, int64_t n_rows, int k, float* out_dist, int32_t* out_ids,
+                        void* stream);
+/* Both stages: nafp_ivf_pq_search_wide for k1 = k * k_factor (k <= 32, k_factor 1 .. 4) into stage1_dist /
+ * stage1_ids (n_query, k1; required), then nafp_ivf_pqr_rerank of those into out_dist / out_ids (n_query, k). */
+int nafp_ivf_pqr_search(const float* query, int64_t n_query, const float* centroids, int nlist, int dim, int nprobe,
+                        const float* pq_centroids, int M, const uint8_t* codes_sorted, const int32_t* offsets,
+                        const int32_t* ids, const int32_t* assign, const uint8_t* codes,
+                        const float* refine_centroids, int M_refine, int nbits_refine, const uint8_t* refine_codes,
+                        int64_t n_rows, int k, int k_factor, float* out_dist, int32_t* out_ids, float* stage1_dist,
+                        int32_t* stage1_ids, int lut, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* In-training mini search test (model/utils/mini_search_subroutines.py): pairwise_distances_for_eval (:28-93;
  * mode 0 = squared L2 clipped at 0 for 'argmin', 1 = dot product for 'argmax'; any dim) into out_scores

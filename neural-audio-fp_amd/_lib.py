@@ -109,6 +109,16 @@ PROTOTYPES = {
                                       c_int, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p]),
     'nafp_ivf_pq_adc_tables': (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
                                        c_void_p, c_void_p]),
+    'nafp_ivf_pq_residuals': (c_int, [c_void_p, c_i64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    'nafp_ivf_refine_encode': (c_int, [c_void_p, c_i64, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'nafp_ivf_pq_wide_workspace_bytes': (c_i64, [c_i64, c_int, c_int, c_int]),
+    'nafp_ivf_pq_search_wide': (c_int, [c_void_p, c_i64, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                        c_int, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p]),
+    'nafp_ivf_pqr_rerank': (c_int, [c_void_p, c_i64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_int, c_int, c_void_p, c_i64, c_int, c_void_p, c_void_p, c_void_p]),
+    'nafp_ivf_pqr_search': (c_int, [c_void_p, c_i64, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_i64, c_int, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p]),
     'nafp_minisearch_scores': (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_void_p, c_void_p]),
     'nafp_minisearch_ranks': (c_int, [c_void_p, c_i64, c_i64, c_int, c_int, c_int, c_void_p, c_void_p]),
     'nafp_lamb_step': (c_int, [c_void_p, c_int, c_float, c_float, c_float, c_float, c_float, c_i64,

@@ -1,5 +1,6 @@
-// Approximate indexes: IVF-Flat and IVF-PQ (faiss IndexIVFFlat / IndexIVFPQ as eval/utils/get_index_faiss.py:64-80 builds
-// them), gfx950.  Opt-in from eval/eval_faiss.py (NAFP_APPROX_INDEX=1); the host side is eval/ivf.py.
+// Approximate indexes: IVF-Flat, IVF-PQ and IVFPQ-RR (faiss IndexIVFFlat / IndexIVFPQ / IndexIVFPQR as
+// eval/utils/get_index_faiss.py:64-80 builds them), gfx950.  Opt-in from eval/eval_faiss.py (NAFP_APPROX_INDEX=1, NAFP_IVFPQ_RR=1);
+// the host side is eval/ivf.py.
 //
 //   ivf_bucket_{count,scan_tiles,offsets,scatter}_kernel   stable counting sort of item ids by key (histogram per 4096-item
 //                              tile, scan over tiles per bucket, scan over buckets, scatter).  The scatter keeps ascending ids
@@ -26,6 +27,12 @@
 //                              then the 4 x K wave results are ranked by counting -- 34 KB of LDS in all, four workgroups per CU
 //   ivf_pq_adc_tables_kernel<DSUB,LUT>  the tables themselves for given (query, list) pairs (ivf_adc_entry, as the scans)
 //   ivf_merge_kernel           per query: the probes' partial lists -> k results (distance asc, id asc), -1 / +inf padding
+//   ivf_pq_scan_wide_kernel<DSUB,LUT>  IVFPQ-RR's first stage: either scan for K <= 128 results (run time); the selection is a
+//                              filter per wave (threshold + LDS candidate buffer, pruned to K by bisection when full)
+//   ivf_pq_residual2_kernel    x - decode(codes): what the refine quantizer is trained on and encodes
+//   ivf_refine_encode_kernel<DR>  per row the nearest of 16 codewords in each of 4 sub-spaces of DR = 16 / 32 / 64 dimensions
+//   ivf_pqr_rerank_kernel<DSUB>  per query: the candidates' list, PQ code and refine code gathered, the fp32 distance to the
+//                              refined reconstruction, the k nearest
 #include "nafp_common.h"
 
 #include <hip/hip_fp16.h>
@@ -488,6 +495,262 @@ __global__ __launch_bounds__(256) void ivf_pq_adc_tables_kernel(const float* __r
     }
 }
 
+// ---- IVFPQ-RR: the wide first stage, the refine codes, the re-rank -------------------------------------------------------
+// The wide scan (K <= 128 at run time).  K sorted entries per lane do not fit registers, so the selection is a filter: every wave
+// keeps a buffer of WIDE_CAP packed (distance, id) candidates in LDS and a threshold, the K-th best it has seen at its last prune.
+// A row whose packed value beats the threshold is appended (slot = the wave's count + the lane's rank in the ballot: the count is
+// wave-uniform, so neither an atomic nor a barrier is needed inside the scan); when an append would not fit, the wave prunes its
+// buffer to its K best: the entries go to registers (WIDE_CAP / 64 per lane), the K-th largest value is found by bisection over the
+// 64 bits of the packed value (per round one compare and one ballot per register), and the survivors are written back compacted.
+// Packed values are distinct (ids are), so after a prune exactly K remain and the threshold is exact.  What a wave holds at the end
+// is the K best of ITS rows whatever the order of appends and the timing of prunes; the 4 x (<= K) wave results are then ranked by
+// counting, as the fp16 scan does, and the K best go out sorted.  Results therefore do not depend on scheduling or batching.
+// LDS: the table, then the four buffers (they overlay the residual, which is dead once the table is built) and 4 counts:
+// fp32 65 536 + 7 680 + 16 = 73 232 B (two workgroups per CU), fp16 32 768 + 7 680 + 16 = 40 464 B (four).
+constexpr int WIDE_CAP = 240;               // candidates per wave buffer (>= 128 + 64: a prune always makes room for one append)
+constexpr int WIDE_REGS = (WIDE_CAP + 63) / 64;
+constexpr int WIDE_KMAX = 128;
+
+// the wave's buffer -> its K best (cnt > K on entry, all values distinct and non-zero); returns the K-th largest value
+__device__ __forceinline__ unsigned long long ivf_wide_prune(unsigned long long* buf, int cnt, int K, int lane) {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    unsigned long long v[WIDE_REGS];
+#pragma unroll
+    for (int j = 0; j < WIDE_REGS; ++j) v[j] = lane + 64 * j < cnt ? buf[lane + 64 * j] : 0ull;
+    unsigned long long t = 0ull;
+#pragma unroll 1
+    for (int bit = 63; bit >= 0; --bit) {                         // the largest t with at least K values >= t
+        const unsigned long long c = t | (1ull << bit);
+        int n = 0;
+#pragma unroll
+        for (int j = 0; j < WIDE_REGS; ++j) n += __popcll(__ballot(v[j] >= c));
+        if (n >= K) t = c;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int at = 0;
+#pragma unroll
+    for (int j = 0; j < WIDE_REGS; ++j) {
+        const bool keep = v[j] >= t;
+        const unsigned long long b = __ballot(keep);
+        if (keep) buf[at + __popcll(b & below)] = v[j];
+        at += __popcll(b);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    return t;
+}
+
+template <int DSUB, int LUT>
+__global__ __launch_bounds__(256) void ivf_pq_scan_wide_kernel(const float* __restrict__ Q, const int* __restrict__ qmap,
+                                                               const int* __restrict__ plist, const float* __restrict__ coarse,
+                                                               const float* __restrict__ pq, const unsigned char* __restrict__ codes,
+                                                               const int* __restrict__ off, const int* __restrict__ ids, int parts, int K,
+                                                               float* __restrict__ pk, int* __restrict__ pi) {
+    constexpr int D = PQ_M * DSUB, NT = PQ_M * PQ_KS, TABLE_FLOATS = LUT == 0 ? NT : NT / 2;
+    extern __shared__ __attribute__((aligned(16))) float lds_wide[];  // table, then [4][WIDE_CAP] u64 (over the residual), [4] counts
+    float* lutf = lds_wide;
+    __half* luth = (__half*)lds_wide;
+    float* rr = lds_wide + TABLE_FLOATS;
+    unsigned long long* cbuf = (unsigned long long*)(lds_wide + TABLE_FLOATS);
+    int* wcnt = (int*)(cbuf + 4 * WIDE_CAP);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t pos = blockIdx.x;
+    const int part = blockIdx.y;
+    const int q = qmap[pos], l = plist[pos];
+    for (int dd = tid; dd < D; dd += 256) rr[dd] = Q[(int64_t)q * D + dd] - coarse[(int64_t)l * D + dd];
+    __syncthreads();
+    for (int e = tid; e < NT; e += 256) {
+        const float ent = ivf_adc_entry<DSUB>(rr, pq, e);
+        if (LUT == 0) lutf[e] = ent;
+        else          luth[e] = __float2half_rn(ent);
+    }
+    __syncthreads();                                              // the residual is dead from here: its place is the buffers'
+    const int o0 = off[l];
+    const int len = off[l + 1] - o0;
+    const int per = (len + parts - 1) / parts;
+    const int r0 = std::min(len, part * per), r1 = std::min(len, r0 + per);
+    unsigned long long* buf = cbuf + wave * WIDE_CAP;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    unsigned long long thr = 0ull;                                // a candidate must beat it (0: nothing yet)
+    float thr_key = -INFINITY;
+    int cnt = 0;
+    uint4 n0 = make_uint4(0u, 0u, 0u, 0u), n1 = n0, n2 = n0, n3 = n0;     // the next row's codes, loaded a row ahead
+    if (r0 + tid < r1) {
+        const uint4* cp = (const uint4*)(codes + (int64_t)(o0 + r0 + tid) * PQ_M);
+        n0 = cp[0]; n1 = cp[1]; n2 = cp[2]; n3 = cp[3];
+    }
+    for (int rb = r0; rb < r1; rb += 256) {                       // a uniform trip count: the wave's count stays wave-uniform
+        const int r = rb + tid;
+        const uint4 w0 = n0, w1 = n1, w2 = n2, w3 = n3;
+        if (r + 256 < r1) {
+            const uint4* cp = (const uint4*)(codes + (int64_t)(o0 + r + 256) * PQ_M);
+            n0 = cp[0]; n1 = cp[1]; n2 = cp[2]; n3 = cp[3];
+        }
+        const unsigned w[16] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w, w3.x, w3.y, w3.z, w3.w};
+        float s = 0.f;
+#pragma unroll
+        for (int m = 0; m < PQ_M; ++m) {
+            const unsigned c = (w[m >> 2] >> (8 * (m & 3))) & 255u;
+            if (LUT == 0) s += lutf[m * PQ_KS + c];
+            else          s += __half2float(luth[m * PQ_KS + c]);
+        }
+        const float key = -s;
+        unsigned long long p = 0ull;
+        if (r < r1 && key >= thr_key) p = ivf_pack(key, ids[o0 + r]);     // equal distances: the ids decide, below
+        const bool take = p > thr;
+        const unsigned long long b = __ballot(take);
+        if (b != 0ull) {
+            const int na = __popcll(b);
+            if (cnt + na > WIDE_CAP) {                            // cnt > WIDE_CAP - 64 >= K: prune, then K + na <= WIDE_CAP
+                thr = ivf_wide_prune(buf, cnt, K, lane);
+                thr_key = ivf_unpack_key(thr);
+                cnt = K;
+            }
+            if (take) buf[cnt + __popcll(b & below)] = p;         // (one that no longer beats the new threshold falls at the next prune)
+            cnt += na;
+        }
+    }
+    cnt = __builtin_amdgcn_readfirstlane(cnt);
+    if (cnt > K) { ivf_wide_prune(buf, cnt, K, lane); cnt = K; }
+    if (lane == 0) wcnt[wave] = cnt;
+    __syncthreads();
+    // the 4 x (<= K) wave results ranked by counting (distinct values): rank < K goes out, the rest of the K slots is padding
+    const int c0 = wcnt[0], c1 = wcnt[1], c2 = wcnt[2], c3 = wcnt[3];
+    const int total = c0 + c1 + c2 + c3;
+    const int64_t o = (pos * parts + part) * K;
+    unsigned long long mine[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {                                 // slot s = wave (s / 128), entry (s % 128)
+        const int s = tid + 256 * j, ws = s >> 7, is = s & 127;
+        mine[j] = is < wcnt[ws] ? cbuf[ws * WIDE_CAP + is] : 0ull;
+    }
+    int rank0 = 0, rank1 = 0;
+    for (int w2 = 0; w2 < 4; ++w2) {
+        const int cw = w2 == 0 ? c0 : w2 == 1 ? c1 : w2 == 2 ? c2 : c3;
+        const unsigned long long* bw = cbuf + w2 * WIDE_CAP;
+        for (int i = 0; i < cw; ++i) { const unsigned long long u = bw[i]; rank0 += u > mine[0] ? 1 : 0; rank1 += u > mine[1] ? 1 : 0; }
+    }
+    if (mine[0] != 0ull && rank0 < K) { pk[o + rank0] = ivf_unpack_key(mine[0]); pi[o + rank0] = ivf_unpack_id(mine[0]); }
+    if (mine[1] != 0ull && rank1 < K) { pk[o + rank1] = ivf_unpack_key(mine[1]); pi[o + rank1] = ivf_unpack_id(mine[1]); }
+    if (tid < K && tid >= total) { pk[o + tid] = -INFINITY; pi[o + tid] = -1; }
+}
+
+// out = x - decode(codes): the second-level residuals the refine quantizer is trained on and encodes
+__global__ __launch_bounds__(256) void ivf_pq_residual2_kernel(const float* __restrict__ x, int64_t n, int dim, int dsub,
+                                                               const float* __restrict__ pq, const unsigned char* __restrict__ codes,
+                                                               float* __restrict__ out) {
+    const int64_t e = blockIdx.x * 256ll + threadIdx.x;
+    if (e >= n * dim) return;
+    const int64_t i = e / dim;
+    const int dd = (int)(e - i * dim), m = dd / dsub, u = dd - m * dsub;
+    out[e] = x[e] - pq[((int64_t)m * PQ_KS + codes[i * PQ_M + m]) * dsub + u];
+}
+
+constexpr int RF_M = 4;                     // refine sub-quantizers
+constexpr int RF_KS = 16;                   // codewords each (4 bits)
+
+// per row and refine sub-space the nearest of 16 codewords (equal distances: the smaller code); DR = dim / 4 = 16 / 32 / 64.
+// packed: 2 bytes per row (c0 | c1 << 4, c2 | c3 << 4); else 4 bytes, one code each (the k-means bucketing's keys)
+template <int DR>
+__global__ __launch_bounds__(256) void ivf_refine_encode_kernel(const float* __restrict__ x, int64_t n, const float* __restrict__ refine,
+                                                                int packed, unsigned char* __restrict__ out) {
+    constexpr int D = RF_M * DR;
+    __shared__ __attribute__((aligned(16))) float cb[RF_M * RF_KS * DR];
+    const int tid = threadIdx.x;
+    for (int e = tid; e < RF_M * RF_KS * DR; e += 256) cb[e] = refine[e];
+    __syncthreads();
+    const int64_t i = blockIdx.x * 256ll + tid;
+    if (i >= n) return;
+    const float4* xr = (const float4*)(x + i * D);
+    unsigned code[RF_M];
+#pragma unroll
+    for (int mr = 0; mr < RF_M; ++mr) {
+        float s[RF_KS];
+#pragma unroll
+        for (int j = 0; j < RF_KS; ++j) s[j] = 0.f;
+        const float* c = cb + mr * RF_KS * DR;
+#pragma unroll 2
+        for (int u4 = 0; u4 < DR / 4; ++u4) {
+            const float4 v = xr[mr * (DR / 4) + u4];
+            const float xv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+#pragma unroll
+                for (int j = 0; j < RF_KS; ++j) { const float t = xv[a] - c[j * DR + u4 * 4 + a]; s[j] += t * t; }
+            }
+        }
+        float best = s[0];
+        unsigned bj = 0;
+#pragma unroll
+        for (int j = 1; j < RF_KS; ++j)
+            if (s[j] < best) { best = s[j]; bj = j; }
+        code[mr] = bj;
+    }
+    if (packed) {
+        out[i * 2] = (unsigned char)(code[0] | (code[1] << 4));
+        out[i * 2 + 1] = (unsigned char)(code[2] | (code[3] << 4));
+    } else {
+#pragma unroll
+        for (int mr = 0; mr < RF_M; ++mr) out[i * RF_M + mr] = (unsigned char)code[mr];
+    }
+}
+
+// one workgroup per query, one thread per first-stage candidate: its list, PQ code and refine code are gathered (insertion
+// order arrays), the row is reconstructed and the distance summed in fp32 with the dimension ascending; then the k1 packed
+// (distance, id) values are ranked by counting (equal values, i.e. a candidate named twice: the earlier slot first)
+template <int DSUB>
+__global__ __launch_bounds__(WIDE_KMAX) void ivf_pqr_rerank_kernel(const float* __restrict__ Q, const int* __restrict__ cand, int k1,
+                                                                   const float* __restrict__ coarse, const int* __restrict__ assign,
+                                                                   const float* __restrict__ pq, const unsigned char* __restrict__ codes,
+                                                                   const float* __restrict__ refine, const unsigned char* __restrict__ rcodes,
+                                                                   int64_t n_rows, int k, float* __restrict__ out_dist, int* __restrict__ out_ids) {
+    constexpr int D = PQ_M * DSUB, DR = D / RF_M;
+    __shared__ float qs[D];
+    __shared__ float rf[RF_M * RF_KS * DR];
+    __shared__ unsigned long long cv[WIDE_KMAX];
+    const int tid = threadIdx.x;
+    const int64_t q = blockIdx.x;
+    for (int dd = tid; dd < D; dd += WIDE_KMAX) qs[dd] = Q[q * D + dd];
+    for (int e = tid; e < RF_M * RF_KS * DR; e += WIDE_KMAX) rf[e] = refine[e];
+    __syncthreads();
+    unsigned long long v = 0ull;
+    const int id = tid < k1 ? cand[q * k1 + tid] : -1;
+    if (id >= 0 && id < n_rows) {
+        const float* cr = coarse + (int64_t)assign[id] * D;
+        const uint4* cp = (const uint4*)(codes + (int64_t)id * PQ_M);
+        const uint4 w0 = cp[0], w1 = cp[1], w2 = cp[2], w3 = cp[3];
+        const unsigned w[16] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w, w3.x, w3.y, w3.z, w3.w};
+        const unsigned rc = (unsigned)rcodes[(int64_t)id * 2] | ((unsigned)rcodes[(int64_t)id * 2 + 1] << 8);
+        float s = 0.f;
+#pragma unroll
+        for (int m = 0; m < PQ_M; ++m) {
+            const float* pc = pq + ((int64_t)m * PQ_KS + ((w[m >> 2] >> (8 * (m & 3))) & 255u)) * DSUB;
+            const int mr = m >> 4;                                // DR = 16 * DSUB: 16 PQ sub-spaces per refine sub-space
+            const float* rp = rf + (mr * RF_KS + ((rc >> (4 * mr)) & 15u)) * DR + (m & 15) * DSUB;
+#pragma unroll
+            for (int u = 0; u < DSUB; ++u) {
+                const float rec = (cr[m * DSUB + u] + pc[u]) + rp[u];
+                const float t = qs[m * DSUB + u] - rec;
+                s += t * t;
+            }
+        }
+        v = ivf_pack(-s, id);
+    }
+    cv[tid] = v;
+    __syncthreads();
+    int rank = 0, filled = 0;
+    for (int i = 0; i < k1; ++i) {
+        const unsigned long long u = cv[i];
+        rank += (u > v || (u == v && i < tid)) ? 1 : 0;
+        filled += u != 0ull ? 1 : 0;
+    }
+    if (v != 0ull && rank < k) { out_dist[q * k + rank] = -ivf_unpack_key(v); out_ids[q * k + rank] = ivf_unpack_id(v); }
+    if (tid < k && tid >= filled) { out_dist[q * k + tid] = INFINITY; out_ids[q * k + tid] = -1; }
+}
+
 // one wave per query: the np x slots x K partial results of its probes -> k_out results.  mode 0 (flat): keys are
 // q.x - |x|^2/2 with list-relative row ids (mapped through row_ids); mode 1 (PQ): keys are -distance with global ids.
 __global__ __launch_bounds__(64) void ivf_merge_kernel(const float* __restrict__ pk, const int* __restrict__ pi,
@@ -665,12 +928,13 @@ extern "C" int nafp_ivf_pq_lists(const uint8_t* codes, int64_t n, int M, const i
     return NAFP_OK;
 }
 
-static bool ivf_search_layout(int64_t n_query, int nlist, int nprobe, int k, int kind, IvfSearchLayout* L) {
+// wide: the IVFPQ-RR first stage (kind 1 only), k <= 128 kept as it is; otherwise k <= 32 in the two compiled sizes
+static bool ivf_search_layout(int64_t n_query, int nlist, int nprobe, int k, int kind, IvfSearchLayout* L, bool wide = false) {
     if (n_query < 0 || n_query > (1 << 30) || nlist <= 0 || nlist > IVF_MAX_BUCKETS || nprobe <= 0 || nprobe > 128 || k <= 0 ||
-        k > 32 || (kind != 0 && kind != 1))
+        k > (wide ? WIDE_KMAX : 32) || (kind != 0 && kind != 1) || (wide && kind != 1))
         return false;
     L->np = std::min(nprobe, nlist);
-    L->K = k <= 20 ? 20 : 32;
+    L->K = wide ? k : k <= 20 ? 20 : 32;
     L->n_pairs = n_query * L->np;
     if (L->n_pairs >= ((int64_t)1 << 31)) return false;
     L->parts = ivf_parts(L->n_pairs, L->np, L->K, kind);
@@ -816,4 +1080,113 @@ extern "C" int nafp_ivf_pq_adc_tables(const float* query, int64_t n_query, const
 #undef NAFP_PQ_TABLES
     NAFP_LAUNCH_CHECK();
     return NAFP_OK;
+}
+
+// ---- IVFPQ-RR --------------------------------------------------------------------------------------------------------
+static bool ivf_refine_ok(int dim, int m_refine, int nbits_refine) { return ivf_dim_ok(dim) && m_refine == RF_M && nbits_refine == 4; }
+
+extern "C" int nafp_ivf_pq_residuals(const float* x, int64_t n, int dim, const float* pq_centroids, int M, const uint8_t* codes, float* out,
+                                     void* stream) {
+    if (!x || !pq_centroids || !codes || !out || n < 0) return NAFP_ERR_INVALID_ARG;
+    if (!ivf_dim_ok(dim) || M != PQ_M || n >= ((int64_t)1 << 31)) return NAFP_ERR_UNSUPPORTED;
+    if (n * dim >= ((int64_t)1 << 32)) return NAFP_ERR_UNSUPPORTED;              // one thread per element, fewer than 2^32 per launch
+    if (n == 0) return NAFP_OK;
+    ivf_pq_residual2_kernel<<<(unsigned)((n * dim + 255) / 256), 256, 0, (hipStream_t)stream>>>(x, n, dim, dim / M, pq_centroids, codes, out);
+    NAFP_LAUNCH_CHECK();
+    return NAFP_OK;
+}
+
+extern "C" int nafp_ivf_refine_encode(const float* x, int64_t n, int dim, const float* refine_centroids, int M_refine, int nbits_refine,
+                                      int packed, uint8_t* codes, void* stream) {
+    if (!x || !refine_centroids || !codes || n < 0) return NAFP_ERR_INVALID_ARG;
+    if (!ivf_refine_ok(dim, M_refine, nbits_refine) || (packed != 0 && packed != 1) || n >= ((int64_t)1 << 31)) return NAFP_ERR_UNSUPPORTED;
+    if (n == 0) return NAFP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    if (dim == 64)       ivf_refine_encode_kernel<16><<<grid, 256, 0, st>>>(x, n, refine_centroids, packed, codes);
+    else if (dim == 128) ivf_refine_encode_kernel<32><<<grid, 256, 0, st>>>(x, n, refine_centroids, packed, codes);
+    else                 ivf_refine_encode_kernel<64><<<grid, 256, 0, st>>>(x, n, refine_centroids, packed, codes);
+    NAFP_LAUNCH_CHECK();
+    return NAFP_OK;
+}
+
+extern "C" int64_t nafp_ivf_pq_wide_workspace_bytes(int64_t n_query, int nlist, int nprobe, int k1) {
+    IvfSearchLayout L;
+    return ivf_search_layout(n_query, nlist, nprobe, k1, 1, &L, true) ? L.total : -1;
+}
+
+extern "C" int nafp_ivf_pq_search_wide(const float* query, int64_t n_query, const float* centroids, int nlist, int dim, int nprobe,
+                                       const float* pq_centroids, int M, const uint8_t* codes_sorted, const int32_t* offsets,
+                                       const int32_t* ids, int k1, float* out_dist, int32_t* out_ids, int lut, void* workspace,
+                                       int64_t workspace_bytes, void* stream) {
+    if (!query || !centroids || !pq_centroids || !codes_sorted || !offsets || !ids || !out_dist || !out_ids || !workspace ||
+        n_query < 0 || nlist <= 0 || nprobe <= 0 || k1 <= 0)
+        return NAFP_ERR_INVALID_ARG;
+    IvfSearchLayout L;
+    if (!ivf_dim_ok(dim) || M != PQ_M || !ivf_lut_ok(lut) || !ivf_search_layout(n_query, nlist, nprobe, k1, 1, &L, true)) return NAFP_ERR_UNSUPPORTED;
+    if (n_query == 0) return NAFP_OK;
+    if (workspace_bytes < L.total) return NAFP_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    int rc = ivf_search_front(query, n_query, centroids, nlist, dim, L, ws, st);
+    if (rc != NAFP_OK) return rc;
+    // the table, the four wave buffers (over the residual's 1 KB), four counts
+    const int lds = (lut == NAFP_IVF_LUT_F32 ? PQ_M * PQ_KS * 4 : PQ_M * PQ_KS * 2) + 4 * WIDE_CAP * 8 + 16;
+    const dim3 grid((unsigned)L.n_pairs, (unsigned)L.parts);
+    const int* qm = (const int*)(ws + L.o_qmap);
+    const int* pl = (const int*)(ws + L.o_plist);
+    float* pk = (float*)(ws + L.o_pk);
+    int* pi = (int*)(ws + L.o_pi);
+#define NAFP_PQ_WIDE(DS_, LUT_)                                                                                                 \
+    {                                                                                                                           \
+        NAFP_HIP_CHECK(hipFuncSetAttribute((const void*)ivf_pq_scan_wide_kernel<DS_, LUT_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); \
+        ivf_pq_scan_wide_kernel<DS_, LUT_><<<grid, 256, lds, st>>>(query, qm, pl, centroids, pq_centroids, codes_sorted, offsets, ids, L.parts, L.K, pk, pi); \
+    }
+#define NAFP_PQ_WIDE_L(DS_) { if (lut == NAFP_IVF_LUT_F32) NAFP_PQ_WIDE(DS_, 0) else NAFP_PQ_WIDE(DS_, 1) }
+    const int dsub = dim / PQ_M;
+    if (dsub == 1) NAFP_PQ_WIDE_L(1) else if (dsub == 2) NAFP_PQ_WIDE_L(2) else NAFP_PQ_WIDE_L(4)
+#undef NAFP_PQ_WIDE_L
+#undef NAFP_PQ_WIDE
+    NAFP_LAUNCH_CHECK();
+    return ivf_search_merge(L, ws, n_query, nullptr, nullptr, query, dim, 1, out_dist, out_ids, k1, st);
+}
+
+extern "C" int nafp_ivf_pqr_rerank(const float* query, int64_t n_query, int dim, const int32_t* cand_ids, int k1, const float* centroids,
+                                   const int32_t* assign, const float* pq_centroids, int M, const uint8_t* codes,
+                                   const float* refine_centroids, int M_refine, int nbits_refine, const uint8_t* refine_codes,
+                                   int64_t n_rows, int k, float* out_dist, int32_t* out_ids, void* stream) {
+    if (!query || !cand_ids || !centroids || !assign || !pq_centroids || !codes || !refine_centroids || !refine_codes || !out_dist ||
+        !out_ids || n_query < 0 || n_rows < 0 || k1 <= 0 || k <= 0)
+        return NAFP_ERR_INVALID_ARG;
+    if (!ivf_refine_ok(dim, M_refine, nbits_refine) || M != PQ_M || k1 > WIDE_KMAX || k > 32 || k > k1 || n_query > (1 << 30) ||
+        n_rows >= ((int64_t)1 << 31))
+        return NAFP_ERR_UNSUPPORTED;
+    if (n_query == 0) return NAFP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned grid = (unsigned)n_query;
+#define NAFP_RERANK(DS_)                                                                                                        \
+    ivf_pqr_rerank_kernel<DS_><<<grid, WIDE_KMAX, 0, st>>>(query, cand_ids, k1, centroids, assign, pq_centroids, codes, refine_centroids, \
+                                                           refine_codes, n_rows, k, out_dist, out_ids);
+    const int dsub = dim / PQ_M;
+    if (dsub == 1) NAFP_RERANK(1) else if (dsub == 2) NAFP_RERANK(2) else NAFP_RERANK(4)
+#undef NAFP_RERANK
+    NAFP_LAUNCH_CHECK();
+    return NAFP_OK;
+}
+
+extern "C" int nafp_ivf_pqr_search(const float* query, int64_t n_query, const float* centroids, int nlist, int dim, int nprobe,
+                                   const float* pq_centroids, int M, const uint8_t* codes_sorted, const int32_t* offsets, const int32_t* ids,
+                                   const int32_t* assign, const uint8_t* codes, const float* refine_centroids, int M_refine, int nbits_refine,
+                                   const uint8_t* refine_codes, int64_t n_rows, int k, int k_factor, float* out_dist, int32_t* out_ids,
+                                   float* stage1_dist, int32_t* stage1_ids, int lut, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!stage1_dist || !stage1_ids || !assign || !codes || !refine_centroids || !refine_codes || !out_dist || !out_ids || k <= 0 ||
+        k_factor <= 0 || n_rows < 0)
+        return NAFP_ERR_INVALID_ARG;
+    if (k > 32 || k_factor > 4 || !ivf_refine_ok(dim, M_refine, nbits_refine)) return NAFP_ERR_UNSUPPORTED;
+    const int k1 = k * k_factor;
+    int rc = nafp_ivf_pq_search_wide(query, n_query, centroids, nlist, dim, nprobe, pq_centroids, M, codes_sorted, offsets, ids, k1,
+                                     stage1_dist, stage1_ids, lut, workspace, workspace_bytes, stream);
+    if (rc != NAFP_OK) return rc;
+    return nafp_ivf_pqr_rerank(query, n_query, dim, stage1_ids, k1, centroids, assign, pq_centroids, M, codes, refine_centroids, M_refine,
+                               nbits_refine, refine_codes, n_rows, k, out_dist, out_ids, stream);
 }

@@ -5,7 +5,8 @@ and of `get_index` (eval/utils/get_index_faiss.py:10-121) for index_type 'L2' --
 faiss.IndexFlatL2 -- backed by libnafp's search kernels (include/nafp.h "Search / evaluation").
 With NAFP_APPROX_INDEX=1 in the environment, 'ivf' and 'ivfpq' build real IVF-Flat / IVF-PQ indexes on the device (eval/ivf.py,
 opt-in; `index_used.json` then names the index and its parameters; NAFP_IVFPQ_LUT=f16 gives 'ivfpq' the reference's fp16 lookup
-tables).  Otherwise, and always for IVFPQ-RR, IVFPQ-ONDISK and HNSW,
+tables; NAFP_IVFPQ_RR=1 next to it makes 'ivfpq-rr' the IVFPQ-RR index, IVF-PQ with refine codes and an exact re-ranking of
+4 x k candidates).  Otherwise, and always for IVFPQ-ONDISK and HNSW,
 the approximate index types are not built: a request for one of them
 (the reference's default is `-i ivfpq`) is SERVED BY THE EXACT SEARCH, with a notice on stderr and the substitution
 recorded in `index_used.json` next to `raw_score.npy` -- on an MI355X the whole [dummy_db ; db] table stays resident
@@ -140,6 +141,12 @@ def approx_index_enabled():
     return os.environ.get('NAFP_APPROX_INDEX', '') == '1'
 
 
+def ivfpq_rr_enabled():
+    """NAFP_IVFPQ_RR=1 next to NAFP_APPROX_INDEX=1: 'ivfpq-rr' builds the IVFPQ-RR index (get_index_faiss.py's IndexIVFPQR:
+    nlist 256, M 64 x 8 bits, refine 4 x 4 bits; k_factor 4, faiss's CPU default) instead of being served by the exact search."""
+    return approx_index_enabled() and os.environ.get('NAFP_IVFPQ_RR', '') == '1'
+
+
 def ivfpq_lut():
     """NAFP_IVFPQ_LUT: the ADC table precision of the opted-in 'ivfpq' index, 'f32' (default) or 'f16' (the reference's
     useFloat16 lookup tables)."""
@@ -156,13 +163,18 @@ def get_index(index_type, train_data, train_data_shape, use_gpu=True, max_nitem_
         if not use_gpu:
             raise NotImplementedError('--nogpu: this build has no CPU search path')
         return FlatL2Index(int(train_data_shape[1]))
-    if mode in APPROX_INDEX_PARAMS and approx_index_enabled():
+    if (mode in APPROX_INDEX_PARAMS and approx_index_enabled()) or (mode == 'ivfpq-rr' and ivfpq_rr_enabled()):
         if not use_gpu:
             raise NotImplementedError('--nogpu: this build has no CPU search path')
-        from .ivf import IVFFlatIndex, IVFPQIndex, training_subset
-        p = APPROX_INDEX_PARAMS[mode]
+        from .ivf import IVFFlatIndex, IVFPQIndex, IVFPQRIndex, training_subset
+        p = APPROX_INDEX_PARAMS['ivfpq' if mode == 'ivfpq-rr' else mode]
         d = int(train_data_shape[1])
-        index = IVFFlatIndex(d, p['nlist']) if mode == 'ivf' else IVFPQIndex(d, p['nlist'], p['M'], p['nbits'], lut=ivfpq_lut())
+        if mode == 'ivf':
+            index = IVFFlatIndex(d, p['nlist'])
+        elif mode == 'ivfpq':
+            index = IVFPQIndex(d, p['nlist'], p['M'], p['nbits'], lut=ivfpq_lut())
+        else:
+            index = IVFPQRIndex(d, p['nlist'], p['M'], p['nbits'], 4, 4, lut=ivfpq_lut())
         index.nprobe = p['nprobe']
         start_time = time.time()
         index.train(training_subset(train_data, max_nitem_train, index.seed))

@@ -7,7 +7,9 @@ faiss-shaped surface: `train(x)`, `is_trained`, `add(x)` (repeatedly), `ntotal`,
 rows in insertion order, kept in a FlatL2Index -- the reference's `fake_recon_index`) and, for tests and re-use, `centroids`,
 `pq_centroids`, `probe_device(q)` and `set_params(...)` / explicit k-means initialisations in `train`.  IVF-PQ has a settable
 `lut` ('f32', the default, or 'f16': the ADC tables rounded to binary16 as the reference's GPU index keeps them) and
-`adc_tables(q, pair_query, pair_list)`, the tables themselves.
+`adc_tables(q, pair_query, pair_list)`, the tables themselves.  `IVFPQRIndex` (faiss.IndexIVFPQR, 'ivfpq-rr' with NAFP_IVFPQ_RR=1)
+adds refine codes and a re-ranking of k * k_factor first-stage candidates: `refine_centroids`, `refine_codes()`, `k_factor`,
+`search_stages(q, k)`.
 
 Training is modelled on faiss's CPU defaults (documentation and source as publicly known; faiss is not a dependency, so this is
 the project's contract rather than a checked copy).  Every constant of it is below.  torch only allocates and copies here; the
@@ -28,11 +30,15 @@ SPLIT_EPS = 1.0 / 1024                   # empty-cluster split: the two copies a
 MAX_NPROBE = 128
 MAX_K = 32
 MAX_NLIST = 16384
+REFINE_M = 4                             # IVFPQ-RR: refine sub-quantizers ...
+REFINE_KS = 16                           # ... of 2^4 codewords each
+MAX_K_FACTOR = 4                         # first-stage candidates per result (k * k_factor <= 128)
 LUT_CODES = {'f32': 0, 'f16': 1}         # NAFP_IVF_LUT_F32 / NAFP_IVF_LUT_F16 (include/nafp.h)
 ASSIGN_CHUNK = 1 << 20                   # rows per coarse-assignment launch (the exact kernel's workspace grows with them)
 
 # independent random streams of one seed
 STREAM_TRAIN_SUBSET, STREAM_COARSE, STREAM_COARSE_SPLIT, STREAM_PQ, STREAM_PQ_SPLIT = range(5)
+STREAM_REFINE, STREAM_REFINE_SPLIT = 5, 6   # IVFPQ-RR: the refine quantizer's initial pick and its splits
 
 
 def rng_for(seed, stream):
@@ -123,6 +129,21 @@ class _Dev:
         out = self.empty((n, pq.shape[0]), torch.uint8) if out is None else out
         _lib.check(self.lib.nafp_ivf_pq_encode(_lib.ptr(x), n, d, _lib.ptr(cent_assign), _lib.ptr(coarse), _lib.ptr(pq), pq.shape[0],
                                                _lib.ptr(out), _lib.current_stream()), 'ivf_pq_encode')
+        return out
+
+    def pq_residuals(self, r, pq, codes):
+        """r - decode(codes): the second-level residuals."""
+        out = torch.empty_like(r)
+        _lib.check(self.lib.nafp_ivf_pq_residuals(_lib.ptr(r), r.shape[0], r.shape[1], _lib.ptr(pq), pq.shape[0], _lib.ptr(codes),
+                                                  _lib.ptr(out), _lib.current_stream()), 'ivf_pq_residuals')
+        return out
+
+    def refine_encode(self, r2, refine, packed):
+        """Refine codes of the rows r2: (n, 2) nibble-packed, or (n, 4) one code per byte."""
+        n, d = r2.shape
+        out = self.empty((n, 2 if packed else REFINE_M), torch.uint8)
+        _lib.check(self.lib.nafp_ivf_refine_encode(_lib.ptr(r2), n, d, _lib.ptr(refine), REFINE_M, 4, int(bool(packed)), _lib.ptr(out),
+                                                   _lib.current_stream()), 'ivf_refine_encode')
         return out
 
     def residuals(self, x, assign, cent):
@@ -377,6 +398,10 @@ class IVFPQIndex(_IVFBase):
     def train(self, x, init=None, pq_init=None):
         """x: (n, d).  init: explicit (nlist, d) coarse initialisation; pq_init: explicit (M, 256, dsub) PQ initialisation."""
         self._train_coarse(x, init)
+        self._train_pq(x, pq_init)
+
+    def _train_pq(self, x, pq_init):
+        """Trains the PQ stage; returns its training residuals (after the subsets), on the device."""
         rng = rng_for(self.seed, STREAM_PQ)
         idx = subset_indices(len(x), PQ_MAX_TRAIN, rng)
         xp = _as_device(x if idx is None else _take(x, idx), self.device)
@@ -396,6 +421,7 @@ class IVFPQIndex(_IVFBase):
                                 else pq_init.reshape(self.M, PQ_KS, self.dsub), self.device).clone()
             dev.kmeans(r, pq, PQ_KS, self.M, PQ_ITERS, rng_for(self.seed, STREAM_PQ_SPLIT), lambda c: (dev.pq_encode(r, None, None, c), 1))
         self.pq_centroids = pq
+        return r
 
     def _add_encoded(self, xd, a):
         self._codes = torch.cat([self._codes, self._dev.pq_encode(xd, a, self.centroids, self.pq_centroids)])
@@ -431,3 +457,114 @@ class IVFPQIndex(_IVFBase):
                                                             self.M, LUT_CODES[self._lut], _lib.ptr(out), _lib.current_stream()),
                        'ivf_pq_adc_tables')
         return out
+
+
+class IVFPQRIndex(IVFPQIndex):
+    """faiss.IndexIVFPQR(quantizer, d, nlist, M, nbits, M_refine, nbits_refine): an IVFPQIndex plus a refine product quantizer
+    (M_refine = 4 sub-spaces of 2^4 codewords) of what the PQ stage leaves, x - centroid[list] - pq_decode(code), 2 bytes per row.
+    `search(q, k)`: the IVF-PQ ADC search of this index for k * k_factor candidates (`lut` applies), then those re-ranked by the
+    fp32 distance to their refined reconstruction (include/nafp.h "IVFPQ-RR").  faiss's CPU class is the model."""
+
+    def __init__(self, d, nlist, M=64, nbits=8, M_refine=4, nbits_refine=4, seed=DEFAULT_SEED, device=None, lut='f32', k_factor=4):
+        if M_refine != REFINE_M or nbits_refine != 4:
+            raise NotImplementedError(f'IVFPQ-RR with M_refine = {M_refine}, nbits_refine = {nbits_refine} (this build: 4 x 4 bits)')
+        super().__init__(d, nlist, M, nbits, seed, device, lut)
+        self.M_refine, self.nbits_refine, self.dsub_refine = REFINE_M, 4, d // REFINE_M
+        self.k_factor = k_factor
+        self.refine_centroids = None                           # (4, 16, d / 4) float32 on the device
+        self._rcodes = self._dev.empty((0, 2), torch.uint8)
+
+    @property
+    def is_trained(self):
+        return super().is_trained and self.refine_centroids is not None
+
+    @property
+    def k_factor(self):
+        return self._k_factor
+
+    @k_factor.setter
+    def k_factor(self, v):
+        if int(v) != v or not 1 <= int(v) <= MAX_K_FACTOR:
+            raise NotImplementedError(f'k_factor = {v} (an integer 1 .. {MAX_K_FACTOR})')
+        self._k_factor = int(v)
+
+    @property
+    def index_description(self):
+        tables = ', fp16 tables' if self._lut == 'f16' else ''
+        return (f'IVFPQR (HIP; nlist {self.nlist}, M {self.M}, nbits {self.nbits}, refine {self.M_refine} x {self.nbits_refine} bits, '
+                f'k_factor {self._k_factor}, nprobe {self._nprobe}{tables})')
+
+    def _refine_shape(self, c):
+        shape = (REFINE_M, REFINE_KS, self.dsub_refine)
+        return _as_device(c.reshape(shape) if torch.is_tensor(c) else np.asarray(c, dtype=np.float32).reshape(shape), self.device).clone()
+
+    def set_params(self, centroids, pq_centroids, refine_centroids):
+        super().set_params(centroids, pq_centroids)
+        self.refine_centroids = self._refine_shape(refine_centroids)
+
+    def train(self, x, init=None, pq_init=None, refine_init=None):
+        """As IVFPQIndex.train, then the refine quantizer on the PQ stage's own training residuals r: k-means (16 codewords in each
+        of 4 sub-spaces, PQ_ITERS iterations) of r - decode(encode(r)).  refine_init: an explicit (4, 16, d / 4) initialisation."""
+        self._train_coarse(x, init)
+        r = self._train_pq(x, pq_init)
+        dev = self._dev
+        with torch.cuda.device(self.device):
+            r2 = dev.pq_residuals(r, self.pq_centroids, dev.pq_encode(r, None, None, self.pq_centroids))
+            if refine_init is None:
+                if r2.shape[0] < REFINE_KS:
+                    raise ValueError(f'{r2.shape[0]} training points for {REFINE_KS} refine centroids')
+                pick = torch.from_numpy(rng_for(self.seed, STREAM_REFINE).permutation(r2.shape[0])[:REFINE_KS]).to(self.device)
+                rf = r2[pick].reshape(REFINE_KS, REFINE_M, self.dsub_refine).transpose(0, 1).contiguous()
+            else:
+                rf = self._refine_shape(refine_init)
+            dev.kmeans(r2, rf, REFINE_KS, REFINE_M, PQ_ITERS, rng_for(self.seed, STREAM_REFINE_SPLIT),
+                       lambda c: (dev.refine_encode(r2, c, False), 1))
+        self.refine_centroids = rf
+
+    def _add_encoded(self, xd, a):
+        dev = self._dev
+        codes = dev.pq_encode(xd, a, self.centroids, self.pq_centroids)
+        rcodes = dev.empty((xd.shape[0], 2), torch.uint8)
+        for i0 in range(0, xd.shape[0], ASSIGN_CHUNK):            # the two residual arrays are temporaries: a chunk at a time
+            i1 = min(xd.shape[0], i0 + ASSIGN_CHUNK)
+            r2 = dev.pq_residuals(dev.residuals(xd[i0:i1], a[i0:i1], self.centroids), self.pq_centroids, codes[i0:i1])
+            rcodes[i0:i1] = dev.refine_encode(r2, self.refine_centroids, True)
+        self._codes = torch.cat([self._codes, codes])
+        self._rcodes = torch.cat([self._rcodes, rcodes])
+
+    def refine_codes(self):
+        """(ntotal, 2) uint8 CUDA: the refine codes in insertion order, byte0 = c0 | c1 << 4, byte1 = c2 | c3 << 4."""
+        return self._rcodes
+
+    def search_stages_device(self, q, k):
+        """q: (nq, d) CUDA -> (D1, I1, D, I) CUDA: the first stage's k * k_factor candidates and the k re-ranked results."""
+        q = _lib.require_cuda(q, 'q').float().contiguous()
+        if k > MAX_K or k < 1:
+            raise NotImplementedError(f'k = {k} (the HIP search keeps k <= {MAX_K} results per query)')
+        if self.ntotal == 0:
+            raise ValueError('empty index')
+        L = self._prepare()
+        nq, k1, lib = q.shape[0], int(k) * self._k_factor, self._dev.lib
+        D, I = self._dev.empty((nq, k), torch.float32), self._dev.empty((nq, k), torch.int32)
+        D1, I1 = self._dev.empty((nq, k1), torch.float32), self._dev.empty((nq, k1), torch.int32)
+        need = int(lib.nafp_ivf_pq_wide_workspace_bytes(nq, self.nlist, self._nprobe, k1))
+        if need < 0:
+            raise NotImplementedError(f'k = {k}, k_factor = {self._k_factor}, nprobe = {self._nprobe}')
+        ws = self._dev.empty((need,), torch.uint8)
+        with torch.cuda.device(self.device):
+            _lib.check(lib.nafp_ivf_pqr_search(_lib.ptr(q), nq, _lib.ptr(self.centroids), self.nlist, self.d, self._nprobe,
+                                               _lib.ptr(self.pq_centroids), self.M, _lib.ptr(L['codes']), _lib.ptr(L['offsets']),
+                                               _lib.ptr(L['ids']), _lib.ptr(self._assign), _lib.ptr(self._codes),
+                                               _lib.ptr(self.refine_centroids), self.M_refine, self.nbits_refine, _lib.ptr(self._rcodes),
+                                               self.ntotal, int(k), self._k_factor, _lib.ptr(D), _lib.ptr(I), _lib.ptr(D1), _lib.ptr(I1),
+                                               LUT_CODES[self._lut], _lib.ptr(ws), need, _lib.current_stream()), 'ivf_pqr_search')
+        return D1, I1, D, I
+
+    def search_device(self, q, k):
+        return self.search_stages_device(q, k)[2:]
+
+    def search_stages(self, q, k):
+        """numpy in, (D1, I1, D, I) numpy out (ids int64): `search` plus the first stage it re-ranked."""
+        qd = torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32)).to(self.device)
+        D1, I1, D, I = self.search_stages_device(qd, k)
+        return D1.cpu().numpy(), I1.cpu().numpy().astype(np.int64), D.cpu().numpy(), I.cpu().numpy().astype(np.int64)

@@ -5,10 +5,13 @@ Data: N clustered synthetic fingerprints, d = 128, unit norm: 20 000 random unit
 fingerprints of one song against the rest); queries = nq random rows with noise (0.3 per row, normalised again) -- the noisy
 copies of eval_faiss.  Measures training time (the index's own seeded training subset), `add` rows/s with the rows already
 on the device, the lazy list build, search time for nq queries (k = 20, nprobe = 40) for the exact index, IVF-Flat
-(nlist 400) and IVF-PQ (nlist 256, M 64, nbits 8) in the same process, and 1-recall@1 / 1-recall@20 of both approximate
+(nlist 400), IVF-PQ (nlist 256, M 64, nbits 8) and IVFPQ-RR in the same process, and 1-recall@1 / 1-recall@20 of both approximate
 indexes against the exact one (the exact nearest neighbour ranked first / within the top 20).  IVF-PQ is searched twice on
 the one trained index, with fp32 ADC tables (`ivfpq_*`, the default) and with binary16 ones (`ivfpq_f16_*`, lut = 'f16'): same
-queries, same process, the two precisions timed alternately.
+queries, same process, the two precisions timed alternately.  IVFPQ-RR (`ivfpq_rr_*`: the same IVF-PQ plus 4 x 4-bit refine codes,
+4 k first-stage candidates re-ranked) is trained with the same seed, so its coarse and PQ stages are IVF-PQ's bit for bit; on that
+one index the plain k = 20 search (`IVFPQIndex.search_device`: the k <= 32 scan, `ivfpq_rr_plain_*`) and the two-stage search are
+timed alternately for both table precisions, and the first stage alone (`nafp_ivf_pq_search_wide` at k1 = 80) once more.
 
 usage: python tools/ivf_bench.py [N=10000000] [nq=38000] [reps=3]   (one JSON line at the end)"""
 import json
@@ -21,7 +24,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from neural_audio_fp_amd.eval.eval_faiss import FlatL2Index  # noqa: E402
-from neural_audio_fp_amd.eval.ivf import IVFFlatIndex, IVFPQIndex  # noqa: E402
+from neural_audio_fp_amd import _lib  # noqa: E402
+from neural_audio_fp_amd.eval.ivf import LUT_CODES, IVFFlatIndex, IVFPQIndex, IVFPQRIndex  # noqa: E402
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
 nq = int(sys.argv[2]) if len(sys.argv) > 2 else 38_000
@@ -64,7 +68,22 @@ res['exact_search_s'], (_, Ie) = best_search(ex, q)
 print(f'exact: search {res["exact_search_s"]:.3f} s', flush=True)
 del ex
 
-for name, make in (('ivf', lambda: IVFFlatIndex(d, 400)), ('ivfpq', lambda: IVFPQIndex(d, 256, 64, 8))):
+def first_stage_only(idx, q, k1):
+    """nafp_ivf_pq_search_wide on its own: the wide scan and its merge without the re-rank."""
+    L, lib = idx._prepare(), idx._dev.lib
+    D = torch.empty((q.shape[0], k1), dtype=torch.float32, device=q.device)
+    I = torch.empty((q.shape[0], k1), dtype=torch.int32, device=q.device)
+    need = int(lib.nafp_ivf_pq_wide_workspace_bytes(q.shape[0], idx.nlist, idx.nprobe, k1))
+    ws = torch.empty((need,), dtype=torch.uint8, device=q.device)
+    _lib.check(lib.nafp_ivf_pq_search_wide(_lib.ptr(q), q.shape[0], _lib.ptr(idx.centroids), idx.nlist, idx.d, idx.nprobe,
+                                           _lib.ptr(idx.pq_centroids), idx.M, _lib.ptr(L['codes']), _lib.ptr(L['offsets']), _lib.ptr(L['ids']),
+                                           k1, _lib.ptr(D), _lib.ptr(I), LUT_CODES[idx.lut], _lib.ptr(ws), need, _lib.current_stream()),
+               'ivf_pq_search_wide')
+    return D, I
+
+
+for name, make in (('ivf', lambda: IVFFlatIndex(d, 400)), ('ivfpq', lambda: IVFPQIndex(d, 256, 64, 8)),
+                   ('ivfpq_rr', lambda: IVFPQRIndex(d, 256, 64, 8, 4, 4))):
     idx = make()
     idx.nprobe = nprobe
     res[f'{name}_train_s'], _ = sync_time(lambda: idx.train(x))
@@ -97,6 +116,33 @@ for name, make in (('ivf', lambda: IVFFlatIndex(d, 400)), ('ivfpq', lambda: IVFP
         print(f'ivfpq, fp16 tables: search {res["ivfpq_f16_search_s"]:.3f} s ({res["ivfpq_f16_search_vs_exact"]:.2f} x exact, '
               f'{res["ivfpq_f16_search_vs_f32"]:.2f} x fp32 tables at {res["ivfpq_search_s"]:.3f} s), 1-recall@1 {res["ivfpq_f16_recall_at_1"]:.4f}, '
               f'@20 {res["ivfpq_f16_recall_at_20"]:.4f}, top-1 equal to fp32 tables for {res["ivfpq_f16_same_top1_as_f32"]:.4f}', flush=True)
+    if name == 'ivfpq_rr':                                     # plain k = 20 scan and two-stage search, fp32 / fp16 tables, in turn
+        runs = {('plain', 'f32'): [], ('plain', 'f16'): [], ('rr', 'f32'): [res['ivfpq_rr_search_s']], ('rr', 'f16'): []}
+        found = {}
+        for kind, lut in list(runs) * reps:
+            idx.lut = lut
+            fn = (lambda: IVFPQIndex.search_device(idx, q, k)) if kind == 'plain' else (lambda: idx.search_device(q, k))
+            IVFPQIndex.search_device(idx, q[:256], k) if kind == 'plain' else idx.search_device(q[:256], k)
+            dt, (_, Il) = sync_time(fn)
+            runs[(kind, lut)].append(dt)
+            found[(kind, lut)] = Il
+        for (kind, lut), ts in runs.items():
+            key = f'ivfpq_rr_{"plain_" if kind == "plain" else ""}{lut}'
+            res[f'{key}_search_s'] = min(ts)
+            res[f'{key}_search_times_s'] = ts
+            res[f'{key}_recall_at_1'] = float((found[(kind, lut)][:, :1] == nn).float().mean())
+            res[f'{key}_recall_at_20'] = float((found[(kind, lut)] == nn).any(1).float().mean())
+        for lut in ('f32', 'f16'):
+            idx.lut = lut
+            first_stage_only(idx, q[:256], 4 * k)
+            res[f'ivfpq_rr_{lut}_first_stage_s'] = min(sync_time(lambda: first_stage_only(idx, q, 4 * k))[0] for _ in range(reps))
+            res[f'ivfpq_rr_{lut}_vs_plain'] = res[f'ivfpq_rr_{lut}_search_s'] / res[f'ivfpq_rr_plain_{lut}_search_s']
+            res[f'ivfpq_rr_{lut}_first_stage_vs_plain'] = res[f'ivfpq_rr_{lut}_first_stage_s'] / res[f'ivfpq_rr_plain_{lut}_search_s']
+            print(f'ivfpq_rr, {lut} tables: two-stage search {res[f"ivfpq_rr_{lut}_search_s"]:.3f} s = {res[f"ivfpq_rr_{lut}_vs_plain"]:.3f} x the plain '
+                  f'k = {k} search of the same index ({res[f"ivfpq_rr_plain_{lut}_search_s"]:.3f} s); first stage alone {res[f"ivfpq_rr_{lut}_first_stage_s"]:.3f} s; '
+                  f'1-recall@1 {res[f"ivfpq_rr_{lut}_recall_at_1"]:.4f} (plain {res[f"ivfpq_rr_plain_{lut}_recall_at_1"]:.4f}), '
+                  f'@20 {res[f"ivfpq_rr_{lut}_recall_at_20"]:.4f} (plain {res[f"ivfpq_rr_plain_{lut}_recall_at_20"]:.4f})', flush=True)
+        idx.lut = 'f32'
     print(f'{name}: train {res[f"{name}_train_s"]:.2f} s, add {res[f"{name}_add_s"]:.3f} s ({res[f"{name}_add_rows_per_s"] / 1e6:.1f} M rows/s) '
           f'+ lists {res[f"{name}_lists_s"]:.3f} s, search {res[f"{name}_search_s"]:.3f} s ({res[f"{name}_search_vs_exact"]:.2f} x exact), '
           f'1-recall@1 {res[f"{name}_recall_at_1"]:.4f}, @20 {res[f"{name}_recall_at_20"]:.4f}', flush=True)

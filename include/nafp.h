@@ -624,6 +624,75 @@ int nafp_ivf_pqr_search(const float* query, int64_t n_query, const float* centro
                         int64_t n_rows, int k, int k_factor, float* out_dist, int32_t* out_ids, float* stage1_dist,
                         int32_t* stage1_ids, int lut, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * HNSW (csrc/hnsw.hip; host side eval/hnsw.py; float64 restatement tests/_hnsw_ref.py): faiss IndexHNSWFlat as
+ * get_index_faiss.py:88-96 builds it, with a DETERMINISTIC ROUND-BASED build: every result below is a pure function of
+ * (rows, level draws, parameters), and every loop has a static bound.
+ *
+ * Parameters: M = 16 links per row on levels >= 1, 2 M = 32 on level 0; ef 1 .. 128; k <= 32; dim 64 / 128 / 256;
+ * levels 0 .. 7 (drawn on the host: row i gets min(7, floor(-ln(u_i) / ln M))).  Distances are fp32 squared L2; every
+ * ordering is by (distance, id) ascending.  A link list is in (distance to its owner, id) order, padded with -1.
+ *
+ * The lists of one level are given as (links, slot, n_link_rows, link_stride): row r's list is the 2 M (level 0) or M
+ * int32 at links[(slot ? slot[r] : r) * link_stride]; a slot outside [0, n_link_rows) is a row without lists.
+ * eval/hnsw.py keeps level 0 as (capacity, 32) without a slot map and levels 1 .. 7 as (n_slots, 7, 16) for the rows
+ * of level >= 1 (level l at links_upper + (l - 1) * 16, stride 7 * 16).
+ *
+ * Layer search (faiss's search_bounded_queue): a pool of at most ef (distance, id, expanded) entries in order,
+ * starting with the entry.  Repeat: take the nearest unexpanded entry c (none: stop), mark it, and let the pool
+ * become the ef best of pool U (neighbours of c on that level not in the pool).  Stop also after max_expansions
+ * expansions (nafp_hnsw_default_max_expansions: 4 ef + 256).  A neighbour rejected or evicted once can never enter
+ * later (the pool's last entry only improves), so no visited set is part of the contract.  ef = 1: greedy descent.
+ *
+ * Selection (faiss's shrink heuristic, pruned entries not kept): walk the candidates in order without the owner and
+ * duplicates; accept c unless an accepted a has dist(c, a) < dist(c, owner); stop at the list's length.
+ *
+ * A round inserts rows [row0, row0 + n_new) into the graph of rows < row0, which stays frozen while they search it
+ * (rows of one round do not see each other).  Entry point ep: the row of highest level L among rows < row0, the
+ * smallest id among equals.  Per new row i of level l_i: cur = ep; for level L .. l_i + 1: cur = search(ef 1)[0]; for
+ * level min(l_i, L) .. 0: W = search(ef = efConstruction), list(i, level) = select(i, W), cur = W[0].  Then, per old
+ * row j and level on which new rows chose it: U = old list U those rows; the list becomes U in order if it fits,
+ * select(j, U) otherwise -- a function of the set U alone.  eval/hnsw.py rounds: n_new = min(max(1, row0 / 8), 16384).
+ *
+ * Status: null pointers / negative sizes NAFP_ERR_INVALID_ARG; dim outside 64 / 128 / 256, k > 32, ef > 128, M != 16,
+ * level > 7: NAFP_ERR_UNSUPPORTED (the workspace queries: -1), all before any GPU call.
+ * ------------------------------------------------------------------------------------------- */
+int nafp_hnsw_default_max_expansions(int ef);       /* 4 ef + 256; -1 for ef outside 1 .. 128 */
+int64_t nafp_hnsw_reverse_workspace_bytes(int64_t n_old, int64_t n_new, int M, int level);
+int64_t nafp_hnsw_search_workspace_bytes(int64_t n_query, int ef_search, int k);
+/* Per query row of query (n_query, dim): the layer search of `level` from entries[q] (a row id; outside [0, n_rows): an
+ * empty result) over the rows x (n_rows, dim).  query_levels (or null): a query with query_levels[q] < level searches
+ * with ef = 1 (the descent of a new row above its own levels).  out (n_query, n_out), n_out <= ef: the first n_out
+ * pool entries, padded with +inf / -1.  entries must not overlap out_ids or out_dist: a query's block writes its
+ * results when it ends, while other blocks may not have read their entry yet. */
+int nafp_hnsw_search_layer(const float* x, int64_t n_rows, int dim, const int32_t* links, const int32_t* slot,
+                           int64_t n_link_rows, int64_t link_stride, int M, int level, const float* query,
+                           int64_t n_query, const int32_t* entries, const int32_t* query_levels, int ef,
+                           int max_expansions, int n_out, float* out_dist, int32_t* out_ids, void* stream);
+/* The forward selection of a round on one level: for each new row row0 + i with new_levels[i] >= level its list :=
+ * select(row0 + i, candidates i) from cand (n_new, ef) as nafp_hnsw_search_layer wrote them (in order, -1 ends).
+ * Rows with new_levels[i] < level are left alone. */
+int nafp_hnsw_select_forward(const float* x, int64_t n_rows, int dim, int64_t row0, int64_t n_new,
+                             const int32_t* new_levels, int level, int M, const float* cand_dist,
+                             const int32_t* cand_ids, int ef, int32_t* links, const int32_t* slot, int64_t n_link_rows,
+                             int64_t link_stride, void* stream);
+/* The reverse links of a round on one level: every row j < row0 that the lists of the new rows (new_levels[i] >=
+ * level) name gets those rows into its list, as above.  Integer atomics count the rows per target, a scan and a
+ * scatter gather them in arbitrary order, and the target's wave walks old list U gathered rows in (distance, id)
+ * order: the new list depends on the set only.  Workspace: nafp_hnsw_reverse_workspace_bytes(row0, n_new, M, level). */
+int nafp_hnsw_reverse_links(const float* x, int64_t n_rows, int dim, int64_t row0, int64_t n_new,
+                            const int32_t* new_levels, int level, int M, int32_t* links, const int32_t* slot,
+                            int64_t n_link_rows, int64_t link_stride, void* workspace, int64_t workspace_bytes,
+                            void* stream);
+/* The search: from `entry` (of level entry_level) the layer search with ef = 1 on levels entry_level .. 1
+ * (links_upper (n_slots, 7, M) and slot; may be null for entry_level 0), then with ef = max(ef_search, k) on level 0
+ * (links0 (>= n_rows, 2 M)); out (n_query, k): its first k entries, padded with +inf / -1.  A query's result does not
+ * depend on the other queries of the call. */
+int nafp_hnsw_search(const float* x, int64_t n_rows, int dim, const int32_t* links0, const int32_t* links_upper,
+                     const int32_t* slot, int64_t n_slots, int M, int entry, int entry_level, const float* query,
+                     int64_t n_query, int ef_search, int k, float* out_dist, int32_t* out_ids, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+
 /* In-training mini search test (model/utils/mini_search_subroutines.py): pairwise_distances_for_eval (:28-93;
  * mode 0 = squared L2 clipped at 0 for 'argmin', 1 = dot product for 'argmax'; any dim) into out_scores
  * (n_query, n_db); then, per sequence length `scope`, the rank of the ground-truth start id

@@ -119,6 +119,17 @@ PROTOTYPES = {
     'nafp_ivf_pqr_search': (c_int, [c_void_p, c_i64, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_i64, c_int, c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p]),
+    'nafp_hnsw_default_max_expansions': (c_int, [c_int]),
+    'nafp_hnsw_reverse_workspace_bytes': (c_i64, [c_i64, c_i64, c_int, c_int]),
+    'nafp_hnsw_search_workspace_bytes': (c_i64, [c_i64, c_int, c_int]),
+    'nafp_hnsw_search_layer': (c_int, [c_void_p, c_i64, c_int, c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_void_p, c_i64, c_void_p,
+                                       c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'nafp_hnsw_select_forward': (c_int, [c_void_p, c_i64, c_int, c_i64, c_i64, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                         c_void_p, c_i64, c_i64, c_void_p]),
+    'nafp_hnsw_reverse_links': (c_int, [c_void_p, c_i64, c_int, c_i64, c_i64, c_void_p, c_int, c_int, c_void_p, c_void_p, c_i64, c_i64,
+                                        c_void_p, c_i64, c_void_p]),
+    'nafp_hnsw_search': (c_int, [c_void_p, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_i64, c_int,
+                                 c_int, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
     'nafp_minisearch_scores': (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_void_p, c_void_p]),
     'nafp_minisearch_ranks': (c_int, [c_void_p, c_i64, c_i64, c_int, c_int, c_int, c_void_p, c_void_p]),
     'nafp_lamb_step': (c_int, [c_void_p, c_int, c_float, c_float, c_float, c_float, c_float, c_i64,

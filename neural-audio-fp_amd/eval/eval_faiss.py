@@ -6,7 +6,8 @@ faiss.IndexFlatL2 -- backed by libnafp's search kernels (include/nafp.h "Search 
 With NAFP_APPROX_INDEX=1 in the environment, 'ivf' and 'ivfpq' build real IVF-Flat / IVF-PQ indexes on the device (eval/ivf.py,
 opt-in; `index_used.json` then names the index and its parameters; NAFP_IVFPQ_LUT=f16 gives 'ivfpq' the reference's fp16 lookup
 tables; NAFP_IVFPQ_RR=1 next to it makes 'ivfpq-rr' the IVFPQ-RR index, IVF-PQ with refine codes and an exact re-ranking of
-4 x k candidates).  Otherwise, and always for IVFPQ-ONDISK and HNSW,
+4 x k candidates; NAFP_HNSW=1 next to it makes 'hnsw' the HNSW graph index of eval/hnsw.py, M 16, efConstruction 80, efSearch 16:
+the reference builds that one on the CPU only, this project on the GPU only).  Otherwise, and always for IVFPQ-ONDISK,
 the approximate index types are not built: a request for one of them
 (the reference's default is `-i ivfpq`) is SERVED BY THE EXACT SEARCH, with a notice on stderr and the substitution
 recorded in `index_used.json` next to `raw_score.npy` -- on an MI355X the whole [dummy_db ; db] table stays resident
@@ -147,6 +148,12 @@ def ivfpq_rr_enabled():
     return approx_index_enabled() and os.environ.get('NAFP_IVFPQ_RR', '') == '1'
 
 
+def hnsw_enabled():
+    """NAFP_HNSW=1 next to NAFP_APPROX_INDEX=1: 'hnsw' builds the HNSW index (get_index_faiss.py:88-96: IndexHNSWFlat, M 16,
+    efConstruction 80, efSearch 16, search_bounded_queue) instead of being served by the exact search."""
+    return approx_index_enabled() and os.environ.get('NAFP_HNSW', '') == '1'
+
+
 def ivfpq_lut():
     """NAFP_IVFPQ_LUT: the ADC table precision of the opted-in 'ivfpq' index, 'f32' (default) or 'f16' (the reference's
     useFloat16 lookup tables)."""
@@ -157,12 +164,22 @@ def ivfpq_lut():
 
 
 def get_index(index_type, train_data, train_data_shape, use_gpu=True, max_nitem_train=2e7):
-    """get_index_faiss.py:10-121 for the exact index (and, opted in, IVF / IVFPQ)."""
+    """get_index_faiss.py:10-121 for the exact index (and, opted in, IVF / IVFPQ / IVFPQ-RR / HNSW).  The reference builds HNSW on
+    the CPU only (faiss has no GPU HNSW); this build has it on the GPU only, so `use_gpu=False` raises for it as for every type."""
     mode = index_type.lower()
     if mode == 'l2':
         if not use_gpu:
             raise NotImplementedError('--nogpu: this build has no CPU search path')
         return FlatL2Index(int(train_data_shape[1]))
+    if mode == 'hnsw' and hnsw_enabled():
+        if not use_gpu:
+            raise NotImplementedError('--nogpu: this build has no CPU search path')
+        from .hnsw import HNSWIndex
+        index = HNSWIndex(int(train_data_shape[1]), 16)          # nothing to train: max_nitem_train is unused, as in the reference
+        index.efConstruction = 80
+        index.efSearch = 16
+        index.requested_type = index_type
+        return index
     if (mode in APPROX_INDEX_PARAMS and approx_index_enabled()) or (mode == 'ivfpq-rr' and ivfpq_rr_enabled()):
         if not use_gpu:
             raise NotImplementedError('--nogpu: this build has no CPU search path')

@@ -39,6 +39,7 @@ ASSIGN_CHUNK = 1 << 20                   # rows per coarse-assignment launch (th
 # independent random streams of one seed
 STREAM_TRAIN_SUBSET, STREAM_COARSE, STREAM_COARSE_SPLIT, STREAM_PQ, STREAM_PQ_SPLIT = range(5)
 STREAM_REFINE, STREAM_REFINE_SPLIT = 5, 6   # IVFPQ-RR: the refine quantizer's initial pick and its splits
+STREAM_HNSW_LEVEL = 7                       # HNSW (eval/hnsw.py): the level draws, one per row in id order
 
 
 def rng_for(seed, stream):

@@ -78,7 +78,8 @@ _EVALUATE = [
                                        "types IVF, IVFPQ (the reference's default), IVFPQ-RR, IVFPQ-ONDISK, HNSW are accepted "
                                        "and served by the same exact search, with a notice.  With NAFP_APPROX_INDEX=1, IVF and IVFPQ "
                                        "are built as real approximate indexes on the GPU, and with NAFP_IVFPQ_RR=1 next to it so is IVFPQ-RR "
-                                       "(IVF-PQ with refine codes and an exact re-ranking).")),
+                                       "(IVF-PQ with refine codes and an exact re-ranking); with NAFP_HNSW=1 next to it HNSW is built "
+                                       "as a graph index on the GPU (M 16, efConstruction 80, efSearch 16).")),
     (('--test_seq_len',), dict(default='1 3 5 9 11 19', type=click.STRING,
                                help='query lengths in segments, space separated (1 3 5 9 11 19 = 1, 2, 3, 5, 6, 10 s)')),
     (('--test_ids', '-t'), dict(default='icassp', type=click.STRING,

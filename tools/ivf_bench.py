@@ -13,7 +13,12 @@ queries, same process, the two precisions timed alternately.  IVFPQ-RR (`ivfpq_r
 one index the plain k = 20 search (`IVFPQIndex.search_device`: the k <= 32 scan, `ivfpq_rr_plain_*`) and the two-stage search are
 timed alternately for both table precisions, and the first stage alone (`nafp_ivf_pq_search_wide` at k1 = 80) once more.
 
-usage: python tools/ivf_bench.py [N=10000000] [nq=38000] [reps=3]   (one JSON line at the end)"""
+`hnsw` mode: the HNSW graph index (eval/hnsw.py, csrc/hnsw.hip; M 16, efConstruction 80 as get_index sets it) on the same kind of
+data: `add` + the round-based build in seconds, search ms per 1,000 queries at efSearch 16 and 64 (k = 20), and recall@1 / @10
+against the exact index (the exact nearest neighbour ranked first / within the first 10).
+
+usage: python tools/ivf_bench.py [N=10000000] [nq=38000] [reps=3]   (one JSON line at the end)
+       python tools/ivf_bench.py hnsw [N=200000] [nq=10000] [reps=3]   (N up to 1 M)"""
 import json
 import os
 import sys
@@ -27,9 +32,12 @@ from neural_audio_fp_amd.eval.eval_faiss import FlatL2Index  # noqa: E402
 from neural_audio_fp_amd import _lib  # noqa: E402
 from neural_audio_fp_amd.eval.ivf import LUT_CODES, IVFFlatIndex, IVFPQIndex, IVFPQRIndex  # noqa: E402
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
-nq = int(sys.argv[2]) if len(sys.argv) > 2 else 38_000
-reps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+args = sys.argv[1:]
+mode = 'hnsw' if args[:1] == ['hnsw'] else 'ivf'
+args = args[1:] if mode == 'hnsw' else args
+N = int(args[0]) if len(args) > 0 else (200_000 if mode == 'hnsw' else 10_000_000)
+nq = int(args[1]) if len(args) > 1 else (10_000 if mode == 'hnsw' else 38_000)
+reps = int(args[2]) if len(args) > 2 else 3
 d, k, nprobe = 128, 20, 40
 
 
@@ -67,6 +75,29 @@ ex.add(x)
 res['exact_search_s'], (_, Ie) = best_search(ex, q)
 print(f'exact: search {res["exact_search_s"]:.3f} s', flush=True)
 del ex
+
+if mode == 'hnsw':
+    from neural_audio_fp_amd.eval.hnsw import HNSWIndex, round_bounds  # noqa: E402
+    idx = HNSWIndex(d)
+    idx.efConstruction = 80
+    res['hnsw_add_s'], _ = sync_time(lambda: idx.add(x))
+    res['hnsw_build_s'], _ = sync_time(idx.build)
+    res['hnsw_rounds'] = len(round_bounds(0, N))
+    res['hnsw_max_level'] = idx.max_level
+    nn = Ie[:, :1]
+    for efs in (16, 64):
+        idx.efSearch = efs
+        dt, (_, Ia) = best_search(idx, q)
+        res[f'hnsw_ef{efs}_search_ms_per_1000'] = dt / nq * 1e6
+        res[f'hnsw_ef{efs}_search_vs_exact'] = dt / res['exact_search_s']
+        res[f'hnsw_ef{efs}_recall_at_1'] = float((Ia[:, :1] == nn).float().mean())
+        res[f'hnsw_ef{efs}_recall_at_10'] = float((Ia[:, :10] == nn).any(1).float().mean())
+        print(f'hnsw efSearch {efs}: {res[f"hnsw_ef{efs}_search_ms_per_1000"]:.2f} ms per 1,000 queries, recall@1 {res[f"hnsw_ef{efs}_recall_at_1"]:.4f}, '
+              f'@10 {res[f"hnsw_ef{efs}_recall_at_10"]:.4f}', flush=True)
+    print(f'hnsw: add {res["hnsw_add_s"]:.3f} s, build {res["hnsw_build_s"]:.2f} s ({res["hnsw_rounds"]} rounds, top level {res["hnsw_max_level"]})', flush=True)
+    print(json.dumps(res))
+    sys.exit(0)
+
 
 def first_stage_only(idx, q, k1):
     """nafp_ivf_pq_search_wide on its own: the wide scan and its merge without the re-rank."""

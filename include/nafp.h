@@ -492,6 +492,31 @@ int nafp_search_seq_scores(const float* query, const float* index, int64_t n_ind
                            const int32_t* task_q0, const int32_t* task_len, int64_t n_tasks,
                            const int32_t* cand, int n_slots, float* out_scores, void* stream);
 
+/* Sequence matching in one launch: from the top-k ids of the segment search to the ranked predictions
+ * (the candidate / unique / score / argsort part of the loop, eval_faiss.py:213-232).  One task t = one
+ * query sequence: rows task_q0[t] .. of `query`, topk_ids (n_query, k) = the search result per query row
+ * (-1 = none).  All device pointers; no workspace.
+ *   - effective length  len_t = min(task_len[t], max_len, n_query - task_q0[t]); a task with task_q0[t]
+ *     outside [0, n_query) or len_t <= 0 has no candidates;
+ *   - candidates of t: the DISTINCT values c = topk_ids[task_q0[t] + i, j] - i over i < len_t, j < k with
+ *     0 <= topk_ids[..] < n_index and c >= 0.  Entries of topk_ids outside [0, n_index) are treated as
+ *     absent (this is also what keeps every read inside `index`);
+ *   - score(c) = mean_{i < min(len_t, n_index - c)} query[task_q0[t] + i] . index[c + i], the fp32
+ *     arithmetic of nafp_search_seq_scores in the same order: the same bits;
+ *   - a candidate whose score is NaN or -inf is dropped;
+ *   - out_ids / out_scores (n_tasks, n_out): the n_out best candidates, score descending, equal scores:
+ *     smaller id first; padding id -1, score -inf.  out_n_cand (n_tasks,) or NULL: the number of distinct
+ *     candidates that were not dropped;
+ *   - bit-identical from run to run; a task's rows do not depend on what else is in the launch.
+ * Status, before any GPU call: NAFP_ERR_INVALID_ARG for a null pointer (out_n_cand excepted) or a negative
+ * size; NAFP_ERR_UNSUPPORTED for dim outside 64 / 128 / 256, k outside 1..32, max_len < 1,
+ * k * max_len > 2048, n_out outside 1..32, n_index >= 2^31 (n_query, n_tasks likewise); n_tasks == 0
+ * returns NAFP_OK without a launch. */
+int nafp_search_seq_match(const float* query, int64_t n_query, const float* index, int64_t n_index, int dim,
+                          const int32_t* topk_ids, int k, const int32_t* task_q0, const int32_t* task_len,
+                          int64_t n_tasks, int max_len, int n_out, int32_t* out_ids, float* out_scores,
+                          int32_t* out_n_cand, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Approximate indexes: IVF-Flat and IVF-PQ (faiss IndexIVFFlat / IndexIVFPQ as
  * eval/utils/get_index_faiss.py:64-80 builds them; opt-in from eval_faiss.py).  Building blocks of

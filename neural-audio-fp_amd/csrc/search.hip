@@ -18,6 +18,7 @@
 //   search_merge_kernel<K>     merges the 2 x splits partial lists of a query (key desc, id asc)
 //   ivf_flat_scan_kernel<D,K>  the same body over one inverted list's rows for the queries that probe it (ivf.hip)
 //   search_seq_score_kernel<D> mean_i q[t+i] . x[c+i] for candidate sequence starts c (eval_faiss.py:221-230)
+//   search_seq_match_kernel<D> top-k ids -> offset-compensated unique candidates -> scores -> the n_out best (eval_faiss.py:213-232)
 #include "nafp_common.h"
 
 #include <algorithm>
@@ -296,6 +297,21 @@ __global__ __launch_bounds__(64) void search_merge_kernel(const float* __restric
     }
 }
 
+// mean_{i < len} Q[q0 + i] . X[c + i] by one wave (every lane returns it): the ONE fp32 summation order of the sequence score --
+// lane l chains fmaf over (i, e = l, l + 64, ..), then the xor-butterfly, then one division.  search_seq_score_kernel and
+// search_seq_match_kernel both call it, so a candidate has the same bits on either path.
+template <int D>
+__device__ __forceinline__ float seq_score_wave(const float* __restrict__ Q, const float* __restrict__ X, int q0, int c, int len,
+                                                int lane) {
+    float s = 0.f;
+    for (int i = 0; i < len; ++i) {
+        const float* qp = Q + (int64_t)(q0 + i) * D; const float* xp = X + (int64_t)(c + i) * D;
+        for (int e = lane; e < D; e += 64) s = fmaf(qp[e], xp[e], s);
+    }
+    s = wave_sum(s);
+    return s / (float)len;
+}
+
 // out[task, slot] = mean_{i < min(len, N - c)} Q[q0 + i] . X[c + i]  for c = cand[task, slot] >= 0, else -inf.
 // One wave per (task, slot).
 template <int D>
@@ -311,13 +327,120 @@ __global__ __launch_bounds__(256) void search_seq_score_kernel(
     if (c < 0 || c >= N) { if (lane == 0) out[w] = -INFINITY; return; }
     const int q0 = task_q0[task];
     const int len = (int)std::min<int64_t>(task_len[task], N - c);
-    float s = 0.f;
-    for (int i = 0; i < len; ++i) {
-        const float* qp = Q + (int64_t)(q0 + i) * D; const float* xp = X + (int64_t)(c + i) * D;
-        for (int e = lane; e < D; e += 64) s = fmaf(qp[e], xp[e], s);
+    const float s = seq_score_wave<D>(Q, X, q0, c, len, lane);
+    if (lane == 0) out[w] = s;
+}
+
+// Sequence matching, from the top-k ids of the segment search to the ranked predictions (eval_faiss.py:213-232), one workgroup
+// of 256 threads per task (include/nafp.h, nafp_search_seq_match, states the contract):
+//   1. gather   slot (i, j) -> c = topk[q0 + i, j] - i into LDS; absent / out-of-range / negative -> SEQM_NONE; the slots are
+//               padded to P, the power of two that holds this task's k * len slots
+//   2. sort     bitonic, ascending, in LDS: equal candidates become runs, SEQM_NONE goes to the end
+//   3. compact  the first element of each run, by ballot and prefix counts (no atomic slot allocation: the unique list is in
+//               ascending id order whatever the timing), into the low word of the key array
+//   4. score    the four waves walk the unique candidates, seq_score_wave once each; a NaN or -inf score drops the candidate
+//               (key 0), every other becomes pack_key(score, c) in place
+//   5. select   wave 0: n_out rounds of arg-max over the keys below the previous round's.  Keys are distinct (ids are), so no
+//               round writes; the score comes back out of the key bit for bit.
+// LDS: P ints + P keys = 12 P bytes (24 KB at the 2048-slot maximum), no global scratch, no atomics.
+constexpr int SEQM_NONE = 0x7fffffff;             // never a candidate: n_index < 2^31 keeps c <= 2^31 - 2
+constexpr int SEQM_MAX_SLOTS = 2048;
+
+__device__ __forceinline__ float unpack_key_score(unsigned long long key) {
+    unsigned u = (unsigned)(key >> 32);
+    u ^= (u >> 31) ? 0x80000000u : 0xffffffffu;
+    return __uint_as_float(u);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void search_seq_match_kernel(
+        const float* __restrict__ Q, int n_query, const float* __restrict__ X, int64_t N, const int* __restrict__ topk, int k,
+        const int* __restrict__ task_q0, const int* __restrict__ task_len, int max_len, int n_out, int* __restrict__ out_ids,
+        float* __restrict__ out_scores, int* __restrict__ out_n_cand, int p_max) {
+    extern __shared__ unsigned long long seqm_keys[];            // [p_max] keys, then [p_max] ints
+    int* ids = (int*)(seqm_keys + p_max);
+    __shared__ int wcnt[4];
+    const int task = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int q0 = task_q0[task];
+    int len = 0;
+    if (q0 >= 0 && q0 < n_query) len = std::max(0, std::min(std::min(task_len[task], max_len), n_query - q0));
+    const int S = k * len;                                         // <= k * max_len <= p_max
+    int P = 1;
+    while (P < S) P <<= 1;
+
+    // 1. gather
+    for (int s = tid; s < P; s += 256) {
+        int c = SEQM_NONE;
+        if (s < S) {
+            const int i = s / k;
+            const int id = topk[(int64_t)(q0 + i) * k + (s - i * k)];
+            if (id >= 0 && id < N && id >= i) c = id - i;
+        }
+        ids[s] = c;
     }
-    s = wave_sum(s);
-    if (lane == 0) out[w] = s / (float)len;
+    __syncthreads();
+    // 2. bitonic sort
+    for (int kk = 2; kk <= P; kk <<= 1)
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < P; i += 256) {
+                const int p = i ^ j;
+                if (p > i) {
+                    const int a = ids[i], b = ids[p];
+                    if ((a > b) == ((i & kk) == 0)) { ids[i] = b; ids[p] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    // 3. compact the run heads, 256 slots at a time
+    int n_uniq = 0;
+    for (int base = 0; base < P; base += 256) {
+        const int i = base + tid;
+        int c = SEQM_NONE;
+        bool head = false;
+        if (i < P) { c = ids[i]; head = c != SEQM_NONE && (i == 0 || ids[i - 1] != c); }
+        const unsigned long long m = __ballot(head);
+        if (lane == 0) wcnt[wave] = __popcll(m);
+        __syncthreads();
+        int before = n_uniq;
+        for (int w = 0; w < wave; ++w) before += wcnt[w];
+        if (head) seqm_keys[before + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned long long)(unsigned)c;
+        n_uniq += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        __syncthreads();
+    }
+    // 4. score each unique candidate once
+    int kept = 0;
+    for (int n = wave; n < n_uniq; n += 4) {
+        const int c = (int)(unsigned)seqm_keys[n];
+        const int l = (int)std::min<int64_t>(len, N - c);
+        const float sc = seq_score_wave<D>(Q, X, q0, c, l, lane);
+        const bool keep = !(sc != sc) && sc != -INFINITY;
+        kept += keep ? 1 : 0;
+        if (lane == 0) seqm_keys[n] = keep ? pack_key(sc, c) : 0ull;
+    }
+    if (lane == 0) wcnt[wave] = kept;
+    __syncthreads();
+    if (wave != 0) return;
+    if (lane == 0 && out_n_cand) out_n_cand[task] = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+    // 5. n_out rounds of arg-max
+    unsigned long long prev = ~0ull;                              // above every key: the low word of a key is <= 0x7fffffff
+    for (int r = 0; r < n_out; ++r) {
+        unsigned long long best = 0ull;
+        for (int n = lane; n < n_uniq; n += 64) {
+            const unsigned long long v = seqm_keys[n];
+            if (v < prev && v > best) best = v;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long ob = __shfl_xor(best, o, 64);
+            if (ob > best) best = ob;
+        }
+        if (lane == 0) {
+            out_ids[(int64_t)task * n_out + r] = best ? 0x7fffffff - (int)(unsigned)best : -1;
+            out_scores[(int64_t)task * n_out + r] = best ? unpack_key_score(best) : -INFINITY;
+        }
+        prev = best;                                              // 0 once the candidates run out: the later rounds find nothing
+    }
 }
 
 template <int D, int K>
@@ -413,6 +536,30 @@ extern "C" int nafp_search_seq_scores(const float* query, const float* index, in
     if (dim == 128) search_seq_score_kernel<128><<<blocks, 256, 0, (hipStream_t)stream>>>(query, index, task_q0, task_len, cand, out_scores, n_index, n_slots, total);
     else if (dim == 256) search_seq_score_kernel<256><<<blocks, 256, 0, (hipStream_t)stream>>>(query, index, task_q0, task_len, cand, out_scores, n_index, n_slots, total);
     else            search_seq_score_kernel<64><<<blocks, 256, 0, (hipStream_t)stream>>>(query, index, task_q0, task_len, cand, out_scores, n_index, n_slots, total);
+    NAFP_LAUNCH_CHECK();
+    return NAFP_OK;
+}
+
+extern "C" int nafp_search_seq_match(const float* query, int64_t n_query, const float* index, int64_t n_index, int dim,
+                                     const int32_t* topk_ids, int k, const int32_t* task_q0, const int32_t* task_len,
+                                     int64_t n_tasks, int max_len, int n_out, int32_t* out_ids, float* out_scores,
+                                     int32_t* out_n_cand, void* stream) {
+    if (!query || !index || !topk_ids || !task_q0 || !task_len || !out_ids || !out_scores || n_query < 0 || n_index < 0 || n_tasks < 0)
+        return NAFP_ERR_INVALID_ARG;
+    if (dim != 64 && dim != 128 && dim != 256) return NAFP_ERR_UNSUPPORTED;
+    if (k < 1 || k > 32 || max_len < 1 || k * (int64_t)max_len > SEQM_MAX_SLOTS || n_out < 1 || n_out > 32) return NAFP_ERR_UNSUPPORTED;
+    if (n_index >= ((int64_t)1 << 31) || n_query >= ((int64_t)1 << 31) || n_tasks >= ((int64_t)1 << 31)) return NAFP_ERR_UNSUPPORTED;
+    if (n_tasks == 0) return NAFP_OK;
+    int p_max = 1;
+    while (p_max < k * max_len) p_max <<= 1;
+    const int lds = p_max * 12;
+    hipStream_t st = (hipStream_t)stream;
+#define NAFP_SEQM(D_) search_seq_match_kernel<D_><<<(unsigned)n_tasks, 256, lds, st>>>(query, (int)n_query, index, n_index, topk_ids, k, \
+        task_q0, task_len, max_len, n_out, out_ids, out_scores, out_n_cand, p_max)
+    if (dim == 128) NAFP_SEQM(128);
+    else if (dim == 256) NAFP_SEQM(256);
+    else NAFP_SEQM(64);
+#undef NAFP_SEQM
     NAFP_LAUNCH_CHECK();
     return NAFP_OK;
 }

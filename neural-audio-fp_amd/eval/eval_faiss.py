@@ -19,7 +19,9 @@ Same inputs ({query, db, dummy_db}.mm + *_shape.npy written by `generate`), same
 length, `test_ids.npy`), same metrics.  Differences in mechanism, not in result:
   * all test ids x sequence lengths are evaluated in ONE batched search over the distinct query
     rows, one batched sequence-score launch, and a vectorised ranking -- not a Python loop with an
-    index.search call per (id, length);
+    index.search call per (id, length); the ranking runs on the host (numpy) unless NAFP_SEQ_MATCH=1 is set: then one kernel
+    per sequence length goes from the top-k ids to the ten ranked predictions on the device (`sequence_match`; same results,
+    `index_used.json` then says "sequence_rank": "device");
   * `dummy_db.mm` is NOT extended on disk (the reference appends `db` to it as its
     "fake_recon_index", eval_faiss.py:158-167): the concatenated table lives on the device;
   * equal scores/distances rank the smaller id first (faiss/argsort leave ties unspecified);
@@ -132,6 +134,43 @@ class FlatL2Index:
                                                         _lib.current_stream()), 'search_seq_scores')
         return out
 
+    def sequence_match(self, q, topk_ids, task_q0, task_len, n_out=10, max_len=None):
+        """The whole sequence match of eval_faiss.py:213-232 in one launch (nafp_search_seq_match, include/nafp.h): per task the
+        distinct offset-compensated candidates of topk_ids (nq, k) int32 (-1 = none), each scored once like `sequence_scores`, and
+        the n_out best (score descending, smaller id first).  q (nq, d) CUDA float32, task_q0 / task_len (T,) int32 CUDA;
+        `max_len` defaults to the maximum of task_len.  Returns (ids (T, n_out) int32, scores (T, n_out) float32, n_cand (T,)
+        int32) on the device; padding is id -1, score -inf."""
+        q = _lib.require_cuda(q, 'q')
+        T = int(task_q0.shape[0])
+        if max_len is None:
+            max_len = max(int(task_len.max()), 1) if T else 1
+        ids = torch.empty((T, int(n_out)), dtype=torch.int32, device=self.device)
+        scores = torch.empty((T, int(n_out)), dtype=torch.float32, device=self.device)
+        n_cand = torch.empty((T,), dtype=torch.int32, device=self.device)
+        if q.dtype != torch.float32 or topk_ids.dtype != torch.int32 or task_q0.dtype != torch.int32 or task_len.dtype != torch.int32:
+            raise TypeError('sequence_match: q float32, topk_ids / task_q0 / task_len int32')
+        if q.dim() != 2 or q.shape[1] != self.d or topk_ids.dim() != 2 or topk_ids.shape[0] != q.shape[0] or task_len.shape[0] != T:
+            raise ValueError('sequence_match: q (nq, d), topk_ids (nq, k), task_q0 and task_len (T,)')
+        q, topk_ids, task_q0, task_len = q.contiguous(), topk_ids.contiguous(), task_q0.contiguous(), task_len.contiguous()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.nafp_search_seq_match(_lib.ptr(q), q.shape[0], _lib.ptr(self._x), self.ntotal, self.d, _lib.ptr(topk_ids),
+                                                       int(topk_ids.shape[1]), _lib.ptr(task_q0), _lib.ptr(task_len), T, int(max_len),
+                                                       int(n_out), _lib.ptr(ids), _lib.ptr(scores), _lib.ptr(n_cand),
+                                                       _lib.current_stream()), 'search_seq_match')
+        return ids, scores, n_cand
+
+
+def seq_match_enabled():
+    """NAFP_SEQ_MATCH=1: the evaluation ranks the sequence candidates on the device (`FlatL2Index.sequence_match`) instead of on
+    the host.  Opt-in; the results are the same."""
+    return os.environ.get('NAFP_SEQ_MATCH', '') == '1'
+
+
+def seq_match_supported(index, k_probe, max_sl):
+    """Whether `index` and the shape fit nafp_search_seq_match: k 1..32, k * max_sl <= 2048 slots, d 64 / 128 / 256."""
+    return (hasattr(index, 'sequence_match') and 1 <= int(k_probe) <= 32 and int(max_sl) >= 1 and int(k_probe) * int(max_sl) <= 2048
+            and getattr(index, 'd', None) in (64, 128, 256))
+
 
 # NAFP_APPROX_INDEX=1: 'ivf' and 'ivfpq' build real approximate indexes (eval/ivf.py) with the reference's parameters
 # (get_index_faiss.py:64-74, nprobe = 40 at :120) instead of being served by the exact search.
@@ -227,13 +266,18 @@ def resolve_test_ids(test_ids, n_query, test_seq_len):
     return np.load(test_ids)
 
 
-def search_and_score(index, query, test_ids, test_seq_len, k_probe, n_dummy, chunk_tasks=1 << 16):
+def search_and_score(index, query, test_ids, test_seq_len, k_probe, n_dummy, chunk_tasks=1 << 16, device_rank=False):
     """The batched form of the loop at eval_faiss.py:199-246.
-    Returns (top1_exact, top1_near, top3_exact, top10_exact, pred_ids (n_test, n_len, 10))."""
+    Returns (top1_exact, top1_near, top3_exact, top10_exact, pred_ids (n_test, n_len, 10)).
+    device_rank: candidates, de-duplication, scores and ranking in one `index.sequence_match` launch per length and chunk; only
+    the (T, 10) predicted ids come back to the host.  Same returns; NotImplementedError where `seq_match_supported` is false."""
     test_ids = np.asarray(test_ids, dtype=np.int64)
     test_seq_len = np.asarray(test_seq_len, dtype=np.int64)
     n_test, n_len = len(test_ids), len(test_seq_len)
     max_sl = int(test_seq_len.max())
+    if device_rank and not seq_match_supported(index, k_probe, max_sl):
+        raise NotImplementedError(f'device_rank: {type(index).__name__} with k_probe {k_probe} x sequence length {max_sl} is outside '
+                                  'nafp_search_seq_match (k <= 32, k * length <= 2048 slots)')
     n_query = len(query)
     assert np.all(test_ids <= n_query)
     # distinct query rows any task touches (python slicing clips at the end of `query`)
@@ -244,9 +288,29 @@ def search_and_score(index, query, test_ids, test_seq_len, k_probe, n_dummy, chu
     dev = index.device
     q_dev = torch.from_numpy(np.ascontiguousarray(query[rows], dtype=np.float32)).to(dev)
     _, I = index.search_device(q_dev, k_probe)                      # (n_rows, k) int32
-    I = I.to(torch.int64)
     out = [np.zeros((n_test, n_len), int) for _ in range(4)]
     preds = -np.ones((n_test, n_len, 10), np.int64)
+
+    def fill(a, b, si, p):
+        gt = (test_ids[a:b] + n_dummy)[:, None]
+        preds[a:b, si, :p.shape[1]] = p
+        out[0][a:b, si] = (p[:, :1] == gt).any(1)
+        out[1][a:b, si] = (np.abs(p[:, :1] - gt) <= 1).any(1) & (p[:, 0] >= 0)
+        out[2][a:b, si] = (p[:, :3] == gt).any(1)
+        out[3][a:b, si] = (p[:, :10] == gt).any(1)
+
+    if device_rank:
+        I = I.to(torch.int32).contiguous()
+        for si, sl in enumerate(test_seq_len.tolist()):
+            sl_eff = np.minimum(sl, n_query - test_ids)              # q = query[t : t+sl] clips at the end
+            for a in range(0, n_test, chunk_tasks):
+                b = min(n_test, a + chunk_tasks)
+                q0 = torch.from_numpy(pos[test_ids[a:b]].astype(np.int32)).to(dev)      # rows of a task are consecutive in q_dev
+                ln = torch.from_numpy(sl_eff[a:b].astype(np.int32)).to(dev)
+                ids, _, _ = index.sequence_match(q_dev, I, q0, ln, n_out=10, max_len=max(int(sl), 1))
+                fill(a, b, si, ids.cpu().numpy().astype(np.int64))
+        return out[0], out[1], out[2], out[3], preds
+    I = I.to(torch.int64)
     S = max_sl * k_probe
     offs = torch.arange(max_sl, device=dev)
     for si, sl in enumerate(test_seq_len.tolist()):
@@ -275,12 +339,7 @@ def search_and_score(index, query, test_ids, test_seq_len, k_probe, n_dummy, chu
             rank = np.lexsort((c, -s), axis=1)[:, :10]
             p = np.take_along_axis(c, rank, 1)
             p[np.take_along_axis(s, rank, 1) == -np.inf] = -1
-            preds[a:b, si, :p.shape[1]] = p
-            gt = (t_ids + n_dummy)[:, None]
-            out[0][a:b, si] = (p[:, :1] == gt).any(1)
-            out[1][a:b, si] = (np.abs(p[:, :1] - gt) <= 1).any(1) & (p[:, 0] >= 0)
-            out[2][a:b, si] = (p[:, :3] == gt).any(1)
-            out[3][a:b, si] = (p[:, :10] == gt).any(1)
+            fill(a, b, si, p)
     return out[0], out[1], out[2], out[3], preds
 
 
@@ -304,8 +363,15 @@ def eval_faiss(emb_dir, emb_dummy_dir=None, index_type='l2', nogpu=False, max_tr
     n_test = len(test_ids)
     print(f'n_test: \033[93m{n_test:n}\033[0m')
     start_time = time.time()
+    device_rank = False
+    if seq_match_enabled():
+        device_rank = seq_match_supported(index, k_probe, int(np.max(test_seq_len)))
+        if not device_rank:
+            import sys
+            print(f'eval: NAFP_SEQ_MATCH=1, but k_probe {k_probe} x sequence length {int(np.max(test_seq_len))} is outside the device '
+                  'ranking (k <= 32, k * length <= 2048 slots); ranking on the host instead.', file=sys.stderr)
     top1_exact, top1_near, top3_exact, top10_exact, _ = search_and_score(index, query, test_ids, test_seq_len, k_probe,
-                                                                        int(dummy_db_shape[0]))
+                                                                        int(dummy_db_shape[0]), device_rank=device_rank)
     torch.cuda.synchronize()
     dt = time.time() - start_time
     rates = [100. * np.mean(m, axis=0) for m in (top1_exact, top1_near, top3_exact, top10_exact)]
@@ -319,17 +385,19 @@ def eval_faiss(emb_dir, emb_dummy_dir=None, index_type='l2', nogpu=False, max_tr
     # search the numbers are not comparable with the reference's IVF-PQ figures: say so NEXT TO them
     import json
     requested = getattr(index, 'requested_type', index_type)
+    rank_note = {'sequence_rank': 'device'} if device_rank else {}      # only when NAFP_SEQ_MATCH=1 served the run
     if hasattr(index, 'index_description'):                     # an approximate index really served the run (opted in)
         with open(f'{emb_dir}/index_used.json', 'w') as f:
             json.dump({'index_type_requested': requested, 'index_type_used': index.index_description, 'substituted': False,
                        'k_probe': int(k_probe), 'note': 'hit rates in raw_score.npy are those of the approximate index '
-                                                        '(NAFP_APPROX_INDEX=1)'}, f, indent=1)
+                                                        '(NAFP_APPROX_INDEX=1)', **rank_note}, f, indent=1)
         print(f'Saved test_ids and raw score to {emb_dir}.')
         return rates
     with open(f'{emb_dir}/index_used.json', 'w') as f:
         json.dump({'index_type_requested': requested, 'index_type_used': 'L2 (exact, HIP FlatL2Index)',
                    'substituted': requested.lower() != 'l2', 'k_probe': int(k_probe),
                    'note': 'approximate faiss index types are served by the exact search: hit rates in raw_score.npy are an '
-                           'upper bound of what the requested index would give' if requested.lower() != 'l2' else 'exact search as requested'}, f, indent=1)
+                           'upper bound of what the requested index would give' if requested.lower() != 'l2' else 'exact search as requested',
+                   **rank_note}, f, indent=1)
     print(f'Saved test_ids and raw score to {emb_dir}.')
     return rates

@@ -324,3 +324,7 @@ class HNSWIndex:
     def sequence_scores(self, q, task_q0, task_len, cand):
         """Scores from the original fp32 rows in insertion order (FlatL2Index.sequence_scores)."""
         return self._flat.sequence_scores(q, task_q0, task_len, cand)
+
+    def sequence_match(self, q, topk_ids, task_q0, task_len, n_out=10, max_len=None):
+        """Ranked sequence candidates from the original fp32 rows in insertion order (FlatL2Index.sequence_match)."""
+        return self._flat.sequence_match(q, topk_ids, task_q0, task_len, n_out=n_out, max_len=max_len)

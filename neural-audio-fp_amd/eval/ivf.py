@@ -310,6 +310,10 @@ class _IVFBase:
         """Scores from the original fp32 rows in insertion order (FlatL2Index.sequence_scores)."""
         return self._flat.sequence_scores(q, task_q0, task_len, cand)
 
+    def sequence_match(self, q, topk_ids, task_q0, task_len, n_out=10, max_len=None):
+        """Ranked sequence candidates from the original fp32 rows in insertion order (FlatL2Index.sequence_match)."""
+        return self._flat.sequence_match(q, topk_ids, task_q0, task_len, n_out=n_out, max_len=max_len)
+
     def list_assignments(self):
         """(ntotal,) int32 CUDA: the list of every row, in insertion order."""
         return self._assign

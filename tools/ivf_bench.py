@@ -17,8 +17,19 @@ timed alternately for both table precisions, and the first stage alone (`nafp_iv
 data: `add` + the round-based build in seconds, search ms per 1,000 queries at efSearch 16 and 64 (k = 20), and recall@1 / @10
 against the exact index (the exact nearest neighbour ranked first / within the first 10).
 
+`seqmatch` mode: the sequence ranking of the evaluation after the segment search, on the host (the default) and on the device
+(`search_and_score(device_rank=True)`, nafp_search_seq_match).  Data: N unit-norm random rows, d = 128; T + 18 queries that are noisy
+copies (0.3 per row, normalised again) of CONSECUTIVE rows, so that sequences exist to be found; test ids 0 .. T - 1, the default
+lengths 1 3 5 9 11 19, k = 20, the exact index.  ONE search of all query rows; the index handed to `search_and_score` answers
+`search_device` from that result, so what is timed is everything after the search.  The two paths alternate in one process, one
+warm-up and `reps` timed calls each, synchronised before every clock read: the whole six-length call (what `evaluate` runs: the host
+path builds 19 x 20 slots per task for every length), then each length in a call of its own (the host path then builds only
+length x 20 slots).  Printed: the times, the mean n_cand / slots per length (the share of slots left after de-duplication), and
+whether the two paths returned the same five arrays.
+
 usage: python tools/ivf_bench.py [N=10000000] [nq=38000] [reps=3]   (one JSON line at the end)
-       python tools/ivf_bench.py hnsw [N=200000] [nq=10000] [reps=3]   (N up to 1 M)"""
+       python tools/ivf_bench.py hnsw [N=200000] [nq=10000] [reps=3]   (N up to 1 M)
+       python tools/ivf_bench.py seqmatch [N=1000000] [T=65536] [reps=3]"""
 import json
 import os
 import sys
@@ -33,10 +44,10 @@ from neural_audio_fp_amd import _lib  # noqa: E402
 from neural_audio_fp_amd.eval.ivf import LUT_CODES, IVFFlatIndex, IVFPQIndex, IVFPQRIndex  # noqa: E402
 
 args = sys.argv[1:]
-mode = 'hnsw' if args[:1] == ['hnsw'] else 'ivf'
-args = args[1:] if mode == 'hnsw' else args
-N = int(args[0]) if len(args) > 0 else (200_000 if mode == 'hnsw' else 10_000_000)
-nq = int(args[1]) if len(args) > 1 else (10_000 if mode == 'hnsw' else 38_000)
+mode = args[0] if args[:1] in (['hnsw'], ['seqmatch']) else 'ivf'
+args = args[1:] if mode != 'ivf' else args
+N = int(args[0]) if len(args) > 0 else {'hnsw': 200_000, 'seqmatch': 1_000_000, 'ivf': 10_000_000}[mode]
+nq = int(args[1]) if len(args) > 1 else {'hnsw': 10_000, 'seqmatch': 65_536, 'ivf': 38_000}[mode]
 reps = int(args[2]) if len(args) > 2 else 3
 d, k, nprobe = 128, 20, 40
 
@@ -57,6 +68,69 @@ def best_search(idx, q):
         times.append(dt)
     return min(times), out
 
+
+def seqmatch():
+    import numpy as np
+    from neural_audio_fp_amd.eval.eval_faiss import search_and_score
+    T, lens, max_sl = nq, (1, 3, 5, 9, 11, 19), 19
+    g = torch.Generator(device='cuda').manual_seed(0)
+    x = torch.empty((N, d), device='cuda')
+    for a in range(0, N, 1 << 20):
+        b = min(N, a + (1 << 20))
+        x[a:b] = torch.nn.functional.normalize(torch.randn((b - a, d), generator=g, device='cuda'), dim=1)
+    n_query = T + max_sl - 1
+    if n_query > N:
+        raise SystemExit(f'T + 18 = {n_query} query rows need at least as many table rows (N = {N})')
+    start = (N - n_query) // 2
+    q = torch.nn.functional.normalize(x[start:start + n_query] + 0.3 * torch.randn((n_query, d), generator=g, device='cuda') / d ** 0.5, dim=1).contiguous()
+    ex = FlatL2Index(d, capacity=N)
+    ex.add(x)
+    ex.search_device(q[:256], k)
+    search_s, (Dq, Iq) = sync_time(lambda: ex.search_device(q, k))
+
+    class AfterTheSearch:
+        """The exact index with the search already done: test ids 0 .. T - 1 touch the query rows 0 .. T + length - 2, in order."""
+        d, device = ex.d, ex.device
+        sequence_scores, sequence_match = ex.sequence_scores, ex.sequence_match
+
+        def search_device(self, qq, kk):
+            assert kk == k and torch.equal(qq, q[:qq.shape[0]])
+            return Dq[:qq.shape[0]], Iq[:qq.shape[0]]
+
+    idx, query, ids = AfterTheSearch(), q.cpu().numpy(), np.arange(T)
+    res = {'mode': 'seqmatch', 'N': N, 'T': T, 'k': k, 'd': d, 'lengths': list(lens), 'reps': reps, 'search_s': search_s}
+
+    def alternate(seq_lens):
+        times, outs = {False: [], True: []}, {}
+        for r in range(reps + 1):                                # r = 0: the warm-up of both
+            for dev_rank in (False, True):
+                dt, outs[dev_rank] = sync_time(lambda: search_and_score(idx, query, ids, seq_lens, k, start, device_rank=dev_rank))
+                if r:
+                    times[dev_rank].append(dt)
+        same = all(np.array_equal(a, b) for a, b in zip(outs[False], outs[True]))
+        return times[False], times[True], same, outs[True]
+
+    host, dev, same, out = alternate(lens)
+    res.update(host_s=min(host), device_s=min(dev), host_times_s=host, device_times_s=dev, outputs_equal=same,
+               host_over_device=min(host) / min(dev), top1_exact_rate=[float(v) for v in out[0].mean(0)])
+    print(f'six lengths, {T} tasks, after the search ({search_s:.3f} s): host ranking {min(host):.3f} s, device ranking {min(dev):.4f} s '
+          f'({min(host) / min(dev):.1f} x), outputs equal: {same}', flush=True)
+    q0, I32 = torch.arange(T, dtype=torch.int32, device='cuda'), Iq.to(torch.int32).contiguous()
+    for sl in lens:
+        host, dev, same_l, _ = alternate((sl,))
+        n_cand = ex.sequence_match(q[:T + sl - 1], I32[:T + sl - 1], q0, torch.full_like(q0, sl), max_len=sl)[2]
+        ratio = float(n_cand.float().mean()) / (sl * k)
+        res[f'len{sl}'] = dict(host_s=min(host), device_s=min(dev), host_times_s=host, device_times_s=dev, outputs_equal=same_l,
+                               n_cand_over_slots=ratio)
+        same = same and same_l
+        print(f'length {sl:2d}: host {min(host):.3f} s, device {min(dev):.4f} s, n_cand / slots {ratio:.3f}, outputs equal: {same_l}', flush=True)
+    res['all_outputs_equal'] = same
+    print(json.dumps(res))
+    sys.exit(0 if same else 1)
+
+
+if mode == 'seqmatch':
+    seqmatch()
 
 g = torch.Generator(device='cuda').manual_seed(0)
 centres = torch.nn.functional.normalize(torch.randn((20000, d), generator=g, device='cuda'), dim=1)

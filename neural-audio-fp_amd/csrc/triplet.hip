@@ -16,7 +16,7 @@ __global__ __launch_bounds__(256) void triplet_rows_kernel(const float* __restri
                                                            float* __restrict__ dist, float* __restrict__ coef,
                                                            float* __restrict__ loss_sum, int nA, int npa, int D, int mode,
                                                            float margin) {
-    extern __shared__ float sh[];                   // anchor row [D] | dist row [M] | red[8]
+    extern __shared__ float sh[];                   // anchor row [D] | signed dist row [M] | red[8]
     const int a = blockIdx.x, tid = threadIdx.x, nP = nA * npa, M = nP + nA;
     float* arow = sh; float* drow = sh + D; float* red = drow + M;
     for (int c = tid; c < D; c += 256) arow[c] = anc[(int64_t)a * D + c];
@@ -30,14 +30,16 @@ __global__ __launch_bounds__(256) void triplet_rows_kernel(const float* __restri
         }
         const float d2 = 2.f * (1.f - dot);
         const float dd = sqrtf((d2 > 0.f ? d2 : 0.f) + TRIPLET_EPS);
-        drow[m] = dd;
+        // dd > 0 always, so the sign bit is free to carry the mask [d2 > 0] of d(dd)/d(dot) = -[d2 > 0] / dd.  It cannot
+        // be recovered from dd: sqrtf(1e-9f)^2 rounds one ulp ABOVE 1e-9f, so dd * dd - eps > 0 also where d2 <= 0.
+        drow[m] = d2 > 0.f ? dd : -dd;
         if (dist) dist[(int64_t)a * M + m] = dd;
     }
     __syncthreads();
     // hardest positive of this anchor: max over its own replicas (the masked matrix is 0 elsewhere, d > 0)
     float hard = 0.f; int hard_m = a * npa;
     if (mode == 0) {
-        for (int k = 0; k < npa; ++k) { const float v = drow[a * npa + k]; if (v > hard) { hard = v; hard_m = a * npa + k; } }
+        for (int k = 0; k < npa; ++k) { const float v = fabsf(drow[a * npa + k]); if (v > hard) { hard = v; hard_m = a * npa + k; } }
     }
     if (mode >= 2) {
         // 'all-balanced' (mode 2, online_triplet_loss.py:215-222): max(mean_pos d - mean_neg d + margin, 0) per anchor;
@@ -49,7 +51,7 @@ __global__ __launch_bounds__(256) void triplet_rows_kernel(const float* __restri
         for (int m = tid; m < M; m += 256) {
             const bool is_pos = m >= a * npa && m < (a + 1) * npa;
             const bool is_neg = !is_pos && m != nP + a;
-            const float dd = drow[m];
+            const float dd = fabsf(drow[m]);
             if (is_pos) { sp += dd; mx = fmaxf(mx, dd); }
             if (is_neg) sn += dd;
         }
@@ -69,17 +71,17 @@ __global__ __launch_bounds__(256) void triplet_rows_kernel(const float* __restri
         const bool active = t > 0.f;
         // hardest positive = FIRST maximum along the row (the sub-gradient tf.reduce_max / torch.max hand out)
         int hard_m = a * npa;
-        for (int k = 0; k < npa; ++k) if (drow[a * npa + k] == mx) { hard_m = a * npa + k; break; }
+        for (int k = 0; k < npa; ++k) if (fabsf(drow[a * npa + k]) == mx) { hard_m = a * npa + k; break; }
         for (int m = tid; m < M; m += 256) {
             const bool is_pos = m >= a * npa && m < (a + 1) * npa;
             const bool is_neg = !is_pos && m != nP + a;
-            const float dd = drow[m];
+            const float sd = drow[m], dd = fabsf(sd);
             float dterm_dd = 0.f;
             if (active) {
                 if (mode == 2) dterm_dd = is_pos ? 1.f / (float)npa : (is_neg ? -1.f / (float)n_an : 0.f);
                 else dterm_dd = m == hard_m ? 1.f : 0.f;
             }
-            const float d2pos = dd * dd - TRIPLET_EPS > 0.f ? 1.f : 0.f;
+            const float d2pos = sd > 0.f ? 1.f : 0.f;
             coef[(int64_t)a * M + m] = inv_a * dterm_dd * (-d2pos / dd);
         }
         if (tid == 0 && active) atomicAdd(loss_sum, t * inv_a);
@@ -90,7 +92,7 @@ __global__ __launch_bounds__(256) void triplet_rows_kernel(const float* __restri
     for (int m = tid; m < M; m += 256) {
         const bool is_pos = m >= a * npa && m < (a + 1) * npa;
         const bool is_neg = !is_pos && m != nP + a;            // an_mask: everything but the own replicas and the anchor itself
-        const float dd = drow[m];
+        const float sd = drow[m], dd = fabsf(sd);
         float term = 0.f, dterm_dd = 0.f;                       // d(term)/d(d[a,m]) (direct dependence)
         if (mode == 0) {                                        // semi-hard: max((hardest - d + margin) * an, 0)
             if (is_neg) { term = hard - dd + margin; if (term > 0.f) { dterm_dd = -1.f; n_active += 1.f; } else term = 0.f; }
@@ -100,7 +102,7 @@ __global__ __launch_bounds__(256) void triplet_rows_kernel(const float* __restri
         }
         lsum += term;
         // d(dd)/d(dot) = -[2(1-dot) > 0] / dd
-        const float d2pos = dd * dd - TRIPLET_EPS > 0.f ? 1.f : 0.f;
+        const float d2pos = sd > 0.f ? 1.f : 0.f;
         coef[(int64_t)a * M + m] = inv * dterm_dd * (-d2pos / dd);
     }
     lsum = wave_sum(lsum); n_active = wave_sum(n_active);
@@ -112,8 +114,8 @@ __global__ __launch_bounds__(256) void triplet_rows_kernel(const float* __restri
         atomicAdd(loss_sum, tot * inv);
         if (mode == 0 && act > 0.f) {
             // the hardest positive carries the gradient of every active term of this row
-            const float dd = drow[hard_m];
-            const float d2pos = dd * dd - TRIPLET_EPS > 0.f ? 1.f : 0.f;
+            const float sd = drow[hard_m], dd = fabsf(sd);
+            const float d2pos = sd > 0.f ? 1.f : 0.f;
             coef[(int64_t)a * M + hard_m] += inv * act * (-d2pos / dd);
         }
     }

@@ -25,6 +25,16 @@ def conv_eye(m, s):
     return out
 
 
+def ranks(mat, s, mode='argmin', gt_id_offset=0):
+    """(nQ, nD) scores -> rank of the ground-truth start t + gt_id_offset of every target t under the eye(s) diagonal sum:
+    its position in the stable argsort, reversed as a whole for 'argmax' (so equal sums put the LARGER id first there)."""
+    conv = conv_eye(mat, s)
+    order = np.argsort(conv, axis=1, kind='stable')
+    if mode == 'argmax':
+        order = order[:, ::-1]
+    return np.array([np.where(order[t] == t + gt_id_offset)[0][0] for t in range(conv.shape[0])])
+
+
 def mini_search_eval(query, db, scopes=(1, 3, 5, 9, 11, 19), mode='argmin', gt_id_offset=0):
     """query (nQ, nAug, d).  Returns ((top1, top3, top10) in %, mean_rank), arrays over the scopes."""
     query = np.asarray(query)
@@ -32,16 +42,8 @@ def mini_search_eval(query, db, scopes=(1, 3, 5, 9, 11, 19), mode='argmin', gt_i
     top = np.zeros((3, len(scopes))); mean_rank = np.zeros(len(scopes))
     mats = [pairwise(query[:, a], db, mode) for a in range(n_augs)]
     for i, s in enumerate(scopes):
-        conv = np.stack([conv_eye(m, s) for m in mats])                  # (n_augs, n_targets, n_db')
-        order = np.argsort(conv, axis=2, kind='stable')
-        if mode == 'argmax':
-            order = order[:, :, ::-1]
-        n_targets = conv.shape[1]
-        ranks = np.zeros((n_augs, n_targets))
-        for t in range(n_targets):
-            for a in range(n_augs):
-                ranks[a, t] = np.where(order[a, t] == t + gt_id_offset)[0][0]
-        mean_rank[i] = ranks.mean()
+        ranks_ = np.stack([ranks(m, s, mode, gt_id_offset) for m in mats])       # (n_augs, n_targets)
+        mean_rank[i] = ranks_.mean()
         for j, k in enumerate((1, 3, 10)):
-            top[j, i] = 100.0 * (ranks < k).mean()
+            top[j, i] = 100.0 * (ranks_ < k).mean()
     return (top[0], top[1], top[2]), mean_rank

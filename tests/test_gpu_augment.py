@@ -93,6 +93,111 @@ def test_special_rows(nafp, corpus):
     assert abs(np.abs(got[0]).max() - 1.0) < 1e-6 and abs(np.abs(got[4]).max() - 1.0) < 1e-6
 
 
+def _edge_arena():
+    """one int16 arena for every seg_len up to 19000: an event that is non-zero at both ends of every window, two noises and three
+    impulse responses (640 decaying taps; 600 taps whose energy sits in the last five; the places where each starts)."""
+    rng = np.random.default_rng(19000)
+    n = 19000
+    t = np.arange(n + 32) / 8000.0                            # every row takes its own window of the event
+    ev = (rng.integers(-2000, 2000, size=n + 32) + 9000 * np.sin(2 * np.pi * 440.0 * t)).astype(np.int16)
+    ev[ev == 0] = 1
+    bg = rng.integers(-6000, 6000, size=n).astype(np.int16)
+    sp = rng.integers(-3000, 3000, size=n).astype(np.int16)
+    ir = (12000 * rng.normal(size=640) * np.exp(-np.arange(640) / 80.0)).astype(np.int16)
+    ir[:4] = [9000, -5000, 3000, -2000]                       # the 1-, 2- and 3-tap responses are not silent
+    ir[596:640] = rng.integers(200, 400, size=44)             # taps 596 (beyond a 597-tap response's last) .. 639 (beyond the 600 kept) matter
+    tail = np.zeros(600, np.int16)
+    tail[595:] = [3000, -7000, 12000, -9000, 5000]
+    parts, at, pos = {}, [], 3                                # odd starts: nothing here needs an aligned window
+    for name, a in (('ev', ev), ('bg', bg), ('sp', sp), ('ir', ir), ('tail', tail)):
+        parts[name] = pos
+        at.append((pos, a))
+        pos += len(a) + 5
+    arena = np.zeros(pos + 8, np.int16)
+    for o, a in at:
+        arena[o:o + len(a)] = a
+    return arena, parts
+
+
+_EDGE_CASES = [  # name, ev_valid (None = seg_len), mix, (nz, nz2) present, snr_db, amp, (ir, ir_len)
+    ('anchor', None, 0, (0, 0), 0.0, 1.0, None),
+    ('anchor with a zero tail', -37, 0, (0, 0), 0.0, 1.0, None),
+    ('anchor without a sample', 0, 0, (0, 0), 0.0, 1.0, None),
+    ('1 tap', None, 0, (0, 0), 0.0, 1.0, ('ir', 1)),
+    ('2 taps', None, 0, (0, 0), 0.0, 1.0, ('ir', 2)),
+    ('3 taps', None, 0, (0, 0), 0.0, 1.0, ('ir', 3)),
+    ('597 taps', None, 0, (0, 0), 0.0, 1.0, ('ir', 597)),
+    ('600 taps after a mix', None, 1, (1, 0), 4.0, 0.5, ('ir', 600)),
+    ('640 taps given, 600 used', None, 0, (0, 0), 0.0, 1.0, ('ir', 640)),
+    ('energy in the last taps: the circular wrap', None, 0, (0, 0), 0.0, 1.0, ('tail', 600)),
+    ('speech without background', None, 1, (0, 1), 6.0, 0.7, None),
+    ('speech without background, then 3 taps', -101, 1, (0, 1), 6.0, 0.7, ('ir', 3)),
+    ('mix without any noise', None, 1, (0, 0), 3.0, 0.3, None),
+    ('mix without any noise, then 597 taps', None, 1, (0, 0), 3.0, 0.3, ('ir', 597)),
+    ('no valid sample, mixed', 0, 1, (1, 1), 5.0, 0.9, None),
+    ('no valid sample, mixed, 600 taps', 0, 1, (1, 0), 5.0, 0.9, ('ir', 600)),
+    ('no valid sample, 600 taps', 0, 0, (0, 0), 0.0, 1.0, ('ir', 600)),
+    ('snr -20 dB', None, 1, (1, 1), -20.0, 0.6, None),
+    ('snr +40 dB, 600 taps', None, 1, (1, 0), 40.0, 0.2, ('tail', 600)),
+]
+
+
+@pytest.mark.parametrize('T', [608, 8000, 16000, 19000])
+def test_rows_at_the_edges_through_the_abi(nafp, T):
+    """nafp_augment_rows on its own arena and row table: the shortest seg_len that holds the 600 taps and their padding, 1 s, 2 s
+    (130 KB of dynamic LDS) and the 19000 limit; 1 / 2 / 3 / 597 / 600 taps, 640 given (the kernel keeps MAX_IR_LENGTH = 600, as the
+    loader does: the oracle gets those 600), a response with its energy in the last taps over an event that is non-zero at both ends
+    of the window (the circular wrap); a speech window without a background window, a mix without any noise, no valid sample with
+    and without a mix, SNR -20 and +40 dB; anchors bit for bit; and an empty table."""
+    import ctypes
+    from neural_audio_fp_amd import _lib
+    lib = _lib.load()
+    arena, at = _edge_arena()
+    rows = np.zeros(len(_EDGE_CASES), dtype=_lib.AUG_ROW_DTYPE)
+    for i, (name, valid, mix, (nz, nz2), snr, amp, ir) in enumerate(_EDGE_CASES):
+        r = rows[i]
+        r['ev_off'] = at['ev'] + i                             # a different window per row
+        r['ev_valid'] = T if valid is None else (T + valid if valid < 0 else valid)
+        r['mix'], r['snr_db'], r['amp'] = mix, snr, amp
+        r['nz_off'], r['nz_valid'] = (at['bg'] + 2 * i, T - 3 * i) if nz else (-1, 0)
+        r['nz2_off'], r['nz2_valid'] = (at['sp'] + i, T - 100) if nz2 else (-1, 0)
+        r['ir_off'], r['ir_len'] = (at[ir[0]], ir[1]) if ir else (-1, 0)
+    assert int((rows['ev_off'] + rows['ev_valid']).max()) <= at['ev'] + 19000 + 32
+    for_oracle = rows.copy()
+    for_oracle['ir_len'] = np.minimum(rows['ir_len'], 600)
+    want = _oracle_rows(arena, for_oracle, T)
+
+    pcm = torch.from_numpy(arena).cuda()
+    d_rows = torch.from_numpy(rows.view(np.uint8).reshape(-1)).cuda()
+    out = torch.full((len(rows), T), float('nan'), device='cuda')
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    assert lib.nafp_augment_rows(ptr(pcm), ptr(d_rows), len(rows), T, ptr(out), stream) == 0
+    got = out.cpu().numpy()
+    err = np.abs(got - want).max(axis=1)
+    for (name, *_), e in zip(_EDGE_CASES, err):
+        print(f'T {T} {name}: {e:.3e}')
+    assert np.isfinite(got).all() and err.max() < 2e-5
+    for i, (name, valid, mix, _, _, _, ir) in enumerate(_EDGE_CASES):
+        if not mix and ir is None:                             # anchors: exact int16 / 2^15, zero tail
+            assert np.array_equal(got[i], want[i].astype(np.float32)), name
+        if valid == 0 and not mix:
+            assert not got[i].any(), name                      # silence stays silence, also through an impulse response
+    peak = np.abs(got).max(axis=1)
+    by_name = {c[0]: i for i, c in enumerate(_EDGE_CASES)}
+    assert abs(peak[by_name['640 taps given, 600 used']] - 1.0) < 1e-6 and abs(peak[by_name['snr +40 dB, 600 taps']] - 1.0) < 1e-6
+    assert abs(peak[by_name['speech without background']] - 0.7) < 1e-6 and abs(peak[by_name['mix without any noise']] - 0.3) < 1e-6
+    # the 640-tap row differs from what all 640 taps would give by far more than the tolerance: the clamp is seen
+    all_taps = _oracle_rows(arena, rows[by_name['640 taps given, 600 used']:][:1], T)[0]
+    assert np.abs(all_taps - want[by_name['640 taps given, 600 used']]).max() > 1e-3
+
+    # an empty table: NAFP_OK, nothing written
+    out.fill_(-3.0)
+    assert lib.nafp_augment_rows(ptr(pcm), ptr(d_rows), 0, T, ptr(out), stream) == 0
+    torch.cuda.synchronize()
+    assert bool((out == -3.0).all())
+
+
 def test_dataset2wav_writes_one_augmented_clip_per_source(nafp, cfg, tmp_path):
     import copy, importlib.util, os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

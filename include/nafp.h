@@ -110,6 +110,66 @@ int nafp_melspec_forward_windows_i16(nafp_melspec* plan, const int16_t* pcm, con
                                      int segment_norm, float* feat, float* group_stat, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Ingest at any sample rate (csrc/resample.hip; numpy restatement tests/_resample_ref.py).  The reference raises on
+ * anything but FS-rate mono files (model/utils/audio_utils.py:160-169) and leaves the conversion to an external tool;
+ * this resampler sits between the PCM upload and nafp_melspec_forward_windows_i16.  EXACT INTEGER ARITHMETIC: an output
+ * sample is a pure function of (file samples, output index), whatever shares its piece, block or launch.
+ *
+ * Ratio: g = gcd(fs_in, fs_out), L = fs_out / g, M = fs_in / g.  Supported: fs_in > fs_out with L <= 320 and
+ * fs_in <= 192000 (11025 .. 192000 -> 8000 among them); fs_in == fs_out (L = M = 1, half = 0, T = 1: the filter is the
+ * single tap 2^30, i.e. the identity for 1 channel and (l + r + 1) >> 1 for 2).  1 or 2 channels, 16-bit PCM.
+ * Filter: Kaiser-windowed sinc designed in float64 at the virtual rate fv = fs_in * L, cut-off fc = 0.95 fs_out / 2,
+ * half = ceil(32 fv / (2 fc)) = ceil(640 fv / (19 fs_out)) (32 zero crossings a side),
+ *   h[v]  = sinc(2 fc v / fv) * I0(8.6 sqrt(1 - (v / half)^2)) / I0(8.6) * (2 fc / fv) * L,   v in [-half, half]
+ *   hq[v] = round(h[v] * 2^30) as int32,   T = ceil((2 half + 1) / L) taps per phase.
+ * Output: n_out = ceil(n_in * L / M); m[j] = x[j] (1 channel) or l[j] + r[j] (2 channels); samples outside the file are zero;
+ *   acc[n] = sum_j hq[n M - j L] * m[j]  over |n M - j L| <= half   (exact in int64: sum |hq| / 2^30 <= 2.23 per phase)
+ *   y[n]   = clamp((acc[n] + 2^(s-1)) >> s, -32768, 32767),  s = 30 (1 channel) / 31 (2 channels), arithmetic shift.
+ * Status: a ratio outside the list NAFP_ERR_UNSUPPORTED, null pointers / negative sizes NAFP_ERR_INVALID_ARG, all before
+ * any GPU call.
+ * ---------------------------------------------------------------------- */
+typedef struct nafp_resample nafp_resample;
+
+/* A run of consecutive output samples of one file.  The raw frames uploaded for it are only what its outputs need
+ * (nafp_resample_input_range); a frame outside them but inside the file is a caller error and is never read. */
+typedef struct nafp_resample_piece {
+    int64_t raw_off;     /* int16 index in the raw arena of the first uploaded frame (interleaved l, r for 2 channels) */
+    int64_t frame0;      /* which frame of the file that is */
+    int64_t n_frames;    /* frames uploaded */
+    int64_t n_in;        /* frames of the whole file */
+    int64_t out0;        /* index in the file's resampled stream of the first output */
+    int64_t out_off;     /* int16 index in the output arena of that output */
+    int32_t n_out;       /* outputs */
+    int32_t channels;    /* 1 or 2 */
+} nafp_resample_piece;
+
+/* Host only. */
+int nafp_resample_geometry(int fs_in, int fs_out, int* L, int* M, int* half, int* T);
+/* Host only: the canonical table (L, T) int32, [phase p][tap t] = hq[p + t L - half], zero where out of range.  Output n
+ * has phase p = (n M + half) mod L and, with jb = (n M + half) div L, is sum_t table[p][t] * m[jb - t].  (The device
+ * layout is the library's own.) */
+int nafp_resample_table_host(int fs_in, int fs_out, int32_t* table_host);
+int64_t nafp_resample_n_out(int64_t n_in, int fs_in, int fs_out);          /* -1: unsupported ratio / negative n_in */
+/* Host only: the frames [*first, *last) of a file of n_in frames that the outputs [n0, n1) read (first == last: none). */
+int nafp_resample_input_range(int64_t n0, int64_t n1, int64_t n_in, int fs_in, int fs_out, int64_t* first,
+                              int64_t* last);
+/* Host only: the checks the kernel makes per piece, on a host copy of the list, before it is uploaded: indices inside
+ * raw_samples / out_samples, the outputs inside the file's n_out, every frame they read uploaded.  NAFP_ERR_INVALID_ARG
+ * for an inconsistent piece, NAFP_ERR_UNSUPPORTED for a channel count other than 1 or 2. */
+int nafp_resample_check_pieces_host(int fs_in, int fs_out, const nafp_resample_piece* pieces_host, int64_t n_pieces,
+                                    int64_t raw_samples, int64_t out_samples);
+/* The plan owns the device table. */
+int nafp_resample_create(nafp_resample** plan, int fs_in, int fs_out);
+int nafp_resample_destroy(nafp_resample* plan);
+/* raw (raw_samples int16) -> out (out_samples int16) for the n_pieces pieces of pieces_dev, all device pointers.  Every
+ * index derived from a piece is checked on the device against raw_samples / out_samples: an inconsistent piece is
+ * skipped, its outputs zeroed (nothing is written for one whose output range leaves the arena).  Int16 outside the
+ * pieces' output ranges is not touched. */
+int nafp_resample_i16(nafp_resample* plan, const int16_t* raw, int64_t raw_samples,
+                      const nafp_resample_piece* pieces_dev, int64_t n_pieces, int16_t* out, int64_t out_samples,
+                      void* stream);
+
+/* ------------------------------------------------------------------------
  * Encoder: FingerPrinter (model/fp/nnfp.py:159-231)
  * ---------------------------------------------------------------------- */
 

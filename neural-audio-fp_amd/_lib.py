@@ -35,6 +35,15 @@ PROTOTYPES = {
     'nafp_melspec_finish': (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_void_p]),
     'nafp_melspec_forward_windows_i16': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_void_p,
                                                  c_void_p, c_void_p]),
+    'nafp_resample_geometry': (c_int, [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                       ctypes.POINTER(c_int)]),
+    'nafp_resample_table_host': (c_int, [c_int, c_int, c_void_p]),
+    'nafp_resample_n_out': (c_i64, [c_i64, c_int, c_int]),
+    'nafp_resample_input_range': (c_int, [c_i64, c_i64, c_i64, c_int, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    'nafp_resample_check_pieces_host': (c_int, [c_int, c_int, c_void_p, c_i64, c_i64, c_i64]),
+    'nafp_resample_create': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int]),
+    'nafp_resample_destroy': (c_int, [c_void_p]),
+    'nafp_resample_i16': (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p]),
     'nafp_encoder_create': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int]),
     'nafp_encoder_create_ex': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int]),
     'nafp_encoder_norm': (c_int, [c_void_p]),
@@ -154,6 +163,11 @@ class Rect(ctypes.Structure):
 AUG_ROW_DTYPE = [('ev_off', '<i8'), ('nz_off', '<i8'), ('nz2_off', '<i8'), ('ir_off', '<i8'), ('ev_valid', '<i4'),
                  ('nz_valid', '<i4'), ('nz2_valid', '<i4'), ('ir_len', '<i4'), ('snr_db', '<f4'), ('amp', '<f4'),
                  ('mix', '<i4'), ('reserved', '<i4')]
+
+
+# nafp_resample_piece (include/nafp.h) as a numpy structured dtype: 56 bytes per piece
+RESAMPLE_PIECE_DTYPE = [('raw_off', '<i8'), ('frame0', '<i8'), ('n_frames', '<i8'), ('n_in', '<i8'), ('out0', '<i8'),
+                        ('out_off', '<i8'), ('n_out', '<i4'), ('channels', '<i4')]
 
 
 class NafpError(RuntimeError):

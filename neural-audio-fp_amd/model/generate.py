@@ -195,8 +195,11 @@ def write_fingerprints(source, embed_fn, arr, group, rank=0, world=1, launch_row
         it = source.iter_windows(r0, r1, launch_rows, alloc=embed_fn.alloc)
         if getattr(embed_fn, 'prefetch', 0) > 0:
             it = _prefetch(it, embed_fn.prefetch)          # file reads of the next launches on a reader thread
-        for start, n, arena, used, off, valid in it:
-            pending.append((start, n, embed_fn.embed_windows(arena, used, off, valid, group)))
+        for start, n, arena, used, off, valid, *work in it:       # NAFP_RESAMPLE=1: + the launch's resampling work (or None)
+            if work and work[0] is not None:
+                pending.append((start, n, embed_fn.embed_windows(arena, used, off, valid, group, pieces=work[0])))
+            else:
+                pending.append((start, n, embed_fn.embed_windows(arena, used, off, valid, group)))
             drain(depth - 1)
     else:
         for start, chunk in source.iter_rows(r0, r1, launch_rows):
@@ -352,7 +355,9 @@ class StreamedEmbedder:
             self.h_pcm[k] = torch.empty((max(n_samples, 1) * 5 // 4,), dtype=torch.int16).pin_memory()
         return self.h_pcm[k].numpy()
 
-    def embed_windows(self, arena, used, seg_offset, seg_valid, group):
+    def embed_windows(self, arena, used, seg_offset, seg_valid, group, pieces=None):
+        """`pieces` (utils/resample.ChunkPieces): `arena` holds raw frames at the files' own rates; they are resampled on this
+        launch's stream into a device arena at the model rate, which the windows then index."""
         k = self.i % len(self.streams)
         self.i += 1
         n = len(seg_offset)
@@ -368,6 +373,8 @@ class StreamedEmbedder:
             pcm_host = torch.from_numpy(arena)              # caller-provided arena (not pinned): still correct
         with torch.cuda.stream(self.streams[k]):
             pcm = pcm_host[:max(used, 1)].cuda(non_blocking=True)
+            if pieces is not None:
+                pcm = pieces.run(pcm)
             d_idx = idx[:, :n].cuda(non_blocking=True)
             self.m_fp.trainable = False
             feat = self.m_pre.forward_windows(pcm, d_idx[0].contiguous(), d_idx[1].to(torch.int32), group_size=group,
@@ -414,6 +421,7 @@ def generate_fingerprint(cfg, checkpoint_name, checkpoint_index, source_root_dir
     embed = StreamedEmbedder(m_pre, m_fp)
 
     sz_check = dict()
+    source_rates = dict()
     for key in ds.keys():
         bsz = int(cfg['BSZ']['TS_BATCH_SZ'])
         n_items = ds[key].n_samples
@@ -429,6 +437,11 @@ def generate_fingerprint(cfg, checkpoint_name, checkpoint_index, source_root_dir
         if rank != 0:
             arr = np.memmap(path, dtype='float32', mode='r+', shape=arr_shape)
         print(f"=== Generating fingerprint from \x1b[1;32m'{key}'\x1b[0m bsz={bsz}, {n_items} items, d={dim} ===")
+        if getattr(ds[key], 'resample', False):
+            from .utils.resample import rates_summary
+            source_rates[key] = rates_summary(ds[key])
+            print(f"'{key}': {source_rates[key]['resampled']} of {source_rates[key]['files']} files are resampled to "
+                  f"{ds[key].fs} Hz mono on the device (rate x channels: files) {source_rates[key]['rates']}")
         write_fingerprints(ds[key], embed, arr, bsz, rank, world)
         arr.flush()
         if dist:
@@ -437,6 +450,10 @@ def generate_fingerprint(cfg, checkpoint_name, checkpoint_index, source_root_dir
         sz_check[key] = len(arr)
         del arr
 
+    if source_rates and rank == 0:          # NAFP_RESAMPLE=1: which rates the fingerprints came from, next to the .mm files
+        import json
+        with open(f'{output_root_dir}/source_rates.json', 'w') as f:
+            json.dump(source_rates, f, indent=1, sort_keys=True)
     if 'custom_source' in ds.keys():
         pass
     elif sz_check['db'] != sz_check['query']:

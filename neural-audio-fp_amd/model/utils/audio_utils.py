@@ -98,6 +98,10 @@ def file_segments(pcm, fs=8000, duration=1., hop=.5):
     return pcm[idx]
 
 
+def _resample_on():
+    return os.environ.get('NAFP_RESAMPLE', '') == '1'
+
+
 class SegmentSource:
     """Ordered segments of a list of WAV files, served in consecutive batches.
 
@@ -112,21 +116,39 @@ class SegmentSource:
         self.seg_len = int(fs * duration)
         self.hop_len = int(np.floor(hop * fs))
         self.n_frames, self.data_offset = [], []
+        # NAFP_RESAMPLE=1: files at other rates / in stereo are taken too and resampled on the device (utils/resample.py);
+        # n_frames is then the length at the model rate, n_in / rate / channels describe the file itself
+        self.resample = _resample_on()
+        self.rate, self.channels, self.n_in, self.resampled = [], [], [], []
         for fn in self.fns:                      # ONE header scan per file (the reference re-opens per segment)
             if fn[-3:] != 'wav':
                 raise NotImplementedError(fn[-3:])
             rate, ch, width, off, nfr = riff_scan(fn)
-            if rate != fs:
-                raise ValueError('Sample rate should be {} but got {}'.format(str(fs), str(rate)))
-            if width != 2 or ch != 1:
-                raise ValueError(f'{fn}: expected 16-bit mono PCM')
-            self.n_frames.append(nfr); self.data_offset.append(off)
+            if self.resample:
+                from . import resample as rs
+                rs.check_file(fn, rate, ch, width, fs)
+                native = rate == fs and ch == 1
+                n_model = nfr if native else rs.n_out(nfr, rate, fs)
+            else:
+                if rate != fs:
+                    raise ValueError('Sample rate should be {} but got {}'.format(str(fs), str(rate)))
+                if width != 2 or ch != 1:
+                    raise ValueError(f'{fn}: expected 16-bit mono PCM')
+                native, n_model = True, nfr
+            self.n_frames.append(n_model); self.data_offset.append(off)
+            self.rate.append(rate); self.channels.append(ch); self.n_in.append(nfr); self.resampled.append(not native)
         counts = [n_segments(nfr, fs, duration, hop) for nfr in self.n_frames]
         self.file_first = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         self.n_samples = int(self.file_first[-1])
 
     def __len__(self):
         return (self.n_samples + self.bsz - 1) // self.bsz
+
+    def _host_pcm(self, f):
+        if self.resampled[f]:
+            raise NotImplementedError(f'{self.fns[f]}: {self.rate[f]} Hz x {self.channels[f]} is resampled on the device only '
+                                      '(iter_windows + StreamedEmbedder.embed_windows); there is no CPU resampler')
+        return read_wav_int16(self.fns[f])
 
     def read_rows(self, row0, row1):
         """int16 (row1-row0, 1, seg_len) for global segment rows [row0, row1)."""
@@ -135,7 +157,7 @@ class SegmentSource:
         r = row0
         while r < row1:
             first, nxt = int(self.file_first[f]), int(self.file_first[f + 1])
-            segs = file_segments(read_wav_int16(self.fns[f]), self.fs, self.duration, self.hop)
+            segs = file_segments(self._host_pcm(f), self.fs, self.duration, self.hop)
             a, b = r - first, min(row1, nxt) - first
             out[r - row0:r - row0 + (b - a), 0] = segs[a:b]
             r += b - a
@@ -158,7 +180,7 @@ class SegmentSource:
             while q < end:
                 f = int(np.searchsorted(self.file_first, q, side='right') - 1)
                 if f != cache_f:
-                    cache = file_segments(read_wav_int16(self.fns[f]), self.fs, self.duration, self.hop)
+                    cache = file_segments(self._host_pcm(f), self.fs, self.duration, self.hop)
                     cache_f = f
                 first, nxt = int(self.file_first[f]), int(self.file_first[f + 1])
                 a, b = q - first, min(end, nxt) - first
@@ -168,7 +190,8 @@ class SegmentSource:
             r = end
 
     def iter_windows(self, row0, row1, rows_per_chunk, alloc=None):
-        """Yield (start_row, n_rows, arena, used, seg_offset, seg_valid) over rows [row0, row1):
+        """Yield (start_row, n_rows, arena, used, seg_offset, seg_valid) -- with NAFP_RESAMPLE=1 a seventh item, the launch's
+        resampling work (utils/resample.ChunkPieces) or None for a launch of model-rate mono files -- over rows [row0, row1):
         the PCM every row needs is read ONCE from each file (contiguous sample range, straight into
         `arena` = alloc(n_samples), e.g. pinned memory) and row i is the window
         arena[seg_offset[i] : seg_offset[i] + seg_len] with samples >= seg_valid[i] meaning zero --
@@ -188,6 +211,10 @@ class SegmentSource:
                 pieces.append((f, a, b, s0, s1, total, q - r))
                 total += (s1 - s0 + 7) // 8 * 8                      # 16-B aligned piece starts
                 q += b - a
+            if self.resample and any(self.resampled[p[0]] for p in pieces):
+                yield (r, n) + self._resample_chunk(pieces, n, total, alloc)
+                r = end
+                continue
             arena = alloc(total) if alloc is not None else np.empty(max(total, 1), np.int16)
             seg_offset = np.empty(n, np.int64)
             seg_valid = np.empty(n, np.int32)
@@ -202,5 +229,39 @@ class SegmentSource:
                 k = np.arange(a, b, dtype=np.int64)
                 seg_offset[o:o + (b - a)] = base + (k - a) * hop_len
                 seg_valid[o:o + (b - a)] = np.clip(self.n_frames[f] - k * hop_len, 0, seg_len)
-            yield r, n, arena, total, seg_offset, seg_valid
+            if self.resample:
+                yield r, n, arena, total, seg_offset, seg_valid, None
+            else:
+                yield r, n, arena, total, seg_offset, seg_valid
             r = end
+
+    def _resample_chunk(self, pieces, n, total, alloc):
+        """A launch that holds a file to resample: (raw arena, used, seg_offset, seg_valid, ChunkPieces).  `arena` then holds the
+        RAW frames every piece's outputs read (nafp_resample_input_range; interleaved for stereo; 16-B aligned piece starts) and
+        seg_offset / seg_valid index the model-rate arena of `total` samples that ChunkPieces.run fills on the device.  Files
+        at the model rate in mono go the same way in such a launch (the identity plan copies them)."""
+        from . import resample as rs
+        seg_len, hop_len = self.seg_len, self.hop_len
+        raw_total, spans = 0, []
+        for f, a, b, s0, s1, base, o in pieces:
+            first, last = rs.input_range(s0, s1, self.n_in[f], self.rate[f], self.fs) if s1 > s0 else (0, 0)
+            spans.append((first, last, raw_total))
+            raw_total += ((last - first) * self.channels[f] + 7) // 8 * 8
+        arena = alloc(raw_total) if alloc is not None else np.empty(max(raw_total, 1), np.int16)
+        seg_offset = np.empty(n, np.int64)
+        seg_valid = np.empty(n, np.int32)
+        by_rate = {}
+        for (f, a, b, s0, s1, base, o), (first, last, raw_base) in zip(pieces, spans):
+            ch = self.channels[f]
+            if last > first:
+                with open(self.fns[f], 'rb', buffering=0) as fh:
+                    fh.seek(self.data_offset[f] + 2 * ch * first)
+                    dst = memoryview(arena[raw_base:raw_base + (last - first) * ch]).cast('B')
+                    if fh.readinto(dst) != 2 * ch * (last - first):
+                        raise IOError(f'{self.fns[f]}: short read')
+            by_rate.setdefault(self.rate[f], []).append((raw_base, first, last - first, self.n_in[f], s0, base, s1 - s0, ch))
+            k = np.arange(a, b, dtype=np.int64)
+            seg_offset[o:o + (b - a)] = base + (k - a) * hop_len
+            seg_valid[o:o + (b - a)] = np.clip(self.n_frames[f] - k * hop_len, 0, seg_len)
+        by_rate = {rate: np.array(rows, dtype=rs.PIECE_DTYPE) for rate, rows in by_rate.items()}
+        return arena, raw_total, seg_offset, seg_valid, rs.ChunkPieces(self.fs, by_rate, total)

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from ... import _lib
-from .audio_utils import n_segments, riff_scan
+from .audio_utils import n_segments, riff_scan, _resample_on
 
 MAX_IR_LENGTH = 600          # dataloader_keras.py:8
 
@@ -54,22 +54,34 @@ def segment_table(n_frames, fs, duration, hop, mode='all'):
 class PcmStore:
     """All samples of a list of 16-bit mono WAV files in ONE int16 array: `start[f]` (first sample of
     file f, 8-sample aligned), `n_frames[f]`.  `.host()` materialises it in numpy (tests, small sets),
-    `.device()` uploads it once through a pinned staging buffer."""
+    `.device()` uploads it once through a pinned staging buffer.  With NAFP_RESAMPLE=1 files at other rates / in stereo are
+    taken too (utils/resample.py): `n_frames` / `start` then count samples at `fs`, `.device()` resamples such a file into its
+    place on the device and `.host()` raises (there is no CPU resampler)."""
 
     def __init__(self, fns, fs, base=0):
         self.fns, self.fs = list(fns), fs
         self.n_frames, self.data_offset, self.start = [], [], []
+        self.resample = _resample_on()
+        self.rate, self.channels, self.n_in, self.resampled = [], [], [], []
         pos = int(base)
         for fn in self.fns:
             if fn[-3:] != 'wav':
                 raise NotImplementedError(fn[-3:])
             rate, ch, width, off, nfr = riff_scan(fn)
-            if rate != fs:
-                raise ValueError('Sample rate should be {} but got {}'.format(str(fs), str(rate)))
-            if width != 2 or ch != 1:
-                raise ValueError(f'{fn}: expected 16-bit mono PCM')
-            self.n_frames.append(nfr); self.data_offset.append(off); self.start.append(pos)
-            pos += (nfr + 7) // 8 * 8
+            if self.resample:
+                from . import resample as rs
+                rs.check_file(fn, rate, ch, width, fs)
+                native = rate == fs and ch == 1
+                n_model = nfr if native else rs.n_out(nfr, rate, fs)
+            else:
+                if rate != fs:
+                    raise ValueError('Sample rate should be {} but got {}'.format(str(fs), str(rate)))
+                if width != 2 or ch != 1:
+                    raise ValueError(f'{fn}: expected 16-bit mono PCM')
+                native, n_model = True, nfr
+            self.n_frames.append(n_model); self.data_offset.append(off); self.start.append(pos)
+            self.rate.append(rate); self.channels.append(ch); self.n_in.append(nfr); self.resampled.append(not native)
+            pos += (n_model + 7) // 8 * 8
         self.base, self.end = int(base), pos
         self.n_frames = np.asarray(self.n_frames, np.int64)
         self.start = np.asarray(self.start, np.int64)
@@ -78,6 +90,9 @@ class PcmStore:
         """dst: int16 numpy view of [base, end) (zero-initialised by the caller)."""
         for f, fn in enumerate(self.fns):
             n = int(self.n_frames[f])
+            if self.resampled[f]:
+                raise NotImplementedError(f'{fn}: {self.rate[f]} Hz x {self.channels[f]} is resampled on the device only '
+                                          '(PcmArena.device); there is no CPU resampler')
             if n:
                 with open(fn, 'rb', buffering=0) as fh:
                     fh.seek(self.data_offset[f])
@@ -103,7 +118,10 @@ class PcmArena:
     def device(self, device=None, piece=1 << 25):
         device = device or torch.device('cuda', torch.cuda.current_device())
         d = torch.zeros((self.total,), dtype=torch.int16, device=device)
-        stage = torch.zeros((min(piece, self.total),), dtype=torch.int16).pin_memory()
+        n_stage = min(piece, self.total)
+        if any(any(s.resampled) for s in self.stores):     # raw frames of a file to resample: several per output sample
+            n_stage = max(n_stage, min(piece, 1 << 22))
+        stage = torch.zeros((n_stage,), dtype=torch.int16).pin_memory()
         for s in self.stores:                      # per store, in pieces of whole files
             f = 0
             while f < len(s.fns):
@@ -117,10 +135,44 @@ class PcmArena:
                 buf[:] = 0
                 sub = PcmStore.__new__(PcmStore)
                 sub.fns, sub.n_frames, sub.data_offset, sub.start, sub.base = s.fns[f:g], s.n_frames[f:g], s.data_offset[f:g], s.start[f:g], a0
+                # files to resample leave their place zero here and are filled below
+                sub.resampled = [False] * (g - f)
+                sub.n_frames = np.where(np.asarray(s.resampled[f:g], bool), 0, sub.n_frames)
                 sub.read_into(buf)
                 d[a0:a1].copy_(stage[:a1 - a0], non_blocking=False)
                 f = g
+            for f in range(len(s.fns)):
+                if s.resampled[f]:
+                    self._resample_file(s, f, d, stage)
+        if any(any(s.resampled) for s in self.stores):
+            torch.cuda.current_stream(device).synchronize()
         return d
+
+    @staticmethod
+    def _resample_file(s, f, d, stage):
+        """File f of store s -> d[start[f] : start[f] + n_frames[f]] at the model rate: its raw frames go through the staging
+        buffer in runs of outputs (each run uploads the frames it reads, nafp_resample_input_range) and one piece per run."""
+        from . import resample as rs
+        plan = rs.plan_for(s.rate[f], s.fs, d.device)
+        ch, n_in, n_total, start = s.channels[f], int(s.n_in[f]), int(s.n_frames[f]), int(s.start[f])
+        # outputs per run: their input span (n M / L frames + the filter's two half-widths) fits the staging buffer
+        margin = 2 * (plan.half // plan.L + 2)
+        room = stage.shape[0] // ch - margin
+        if room * plan.L < plan.M:
+            raise NotImplementedError(f'{s.fns[f]}: staging buffer too small to resample from {s.rate[f]} Hz')
+        step = max(1, min(room * plan.L // plan.M, (1 << 31) - 1))
+        with open(s.fns[f], 'rb', buffering=0) as fh:
+            for n0 in range(0, n_total, step):
+                n1 = min(n_total, n0 + step)
+                first, last = rs.input_range(n0, n1, n_in, s.rate[f], s.fs)
+                k = (last - first) * ch
+                if k:
+                    fh.seek(s.data_offset[f] + 2 * ch * first)
+                    if fh.readinto(memoryview(stage.numpy()[:k]).cast('B')) != 2 * k:
+                        raise IOError(f'{s.fns[f]}: short read')
+                raw = stage[:max(k, 1)].to(d.device, non_blocking=False)
+                piece = np.array([(0, first, last - first, n_in, n0, start + n0, n1 - n0, ch)], dtype=rs.PIECE_DTYPE)
+                plan.run(raw, piece, d)
 
 
 def _randint(rng, low, high, size=None):

@@ -68,6 +68,32 @@ int nafp_mel_filterbank_host(int fs, int n_fft, int n_mels, float f_min, float f
  * every mel filter <= 8 taps wide. */
 int nafp_melspec_create(nafp_melspec** plan, int fs, int seg_len, int n_fft, int hop,
                         int n_mels, float f_min, float f_max);
+/* The same plan for ANY geometry of the front end's config keys (MODEL.FS, STFT_WIN, STFT_HOP, N_MELS, F_MIN, F_MAX, DUR), which
+ * the reference hands to kapre and librosa unrestricted (melspectrogram.py:115-141).  flags:
+ *   0                            exactly nafp_melspec_create
+ *   NAFP_MELSPEC_ANY_GEOMETRY    a geometry nafp_melspec_create refuses is served by the general kernel (csrc/melspec_any.hip);
+ *                                one it serves keeps the tuned kernel
+ *   NAFP_MELSPEC_FORCE_GENERAL   the general kernel for those as well (tests, A/B runs)
+ * General kernel: n_fft a power of two in 128 ... 4096, 1 <= hop <= n_fft (any value: no divisor of n_fft, no power of two needed),
+ * 1 <= n_mels <= 512, seg_len <= 2^22 (shorter than n_fft included), any fs and f_min < f_max, filters of any width; an all-zero
+ * filter yields log10(0.06).  Everything else is NAFP_ERR_UNSUPPORTED (bad pointers / sizes / flag bits NAFP_ERR_INVALID_ARG), decided
+ * before any HIP call.  Either kind of plan goes to every nafp_melspec_* entry point below and has the same contract: float32 or
+ * int16 input with the same bytes out, windows, NAFP_MELSPEC_DEFER, a segment's raw log-mel a pure function of its samples.
+ *
+ * nafp_melspec_plan_host: host only (works in a process without a GPU), what create_ex would build.  Same status as create_ex;
+ * record_host receives NAFP_MELSPEC_PLAN_FIELDS values:
+ *   [0] kernel: 0 tuned (melspec_r16_kernel), 1 general (melspec_any_kernel)   [1] n_frames = 1 + seg_len / hop   [2] bins = n_fft / 2 + 1
+ *   [3] non-zero weights of the mel bank   [4] taps of its widest filter   [5] its all-zero filters   [6] frames per workgroup
+ *   [7] dynamic LDS bytes per workgroup   [8] chunks of [6] frames per segment (grid y; above 65,535 a workgroup takes several)   [9] frame pairs a workgroup transforms at a time.
+ * tests/test_melspec_any_host.py holds the records.  nafp_melspec_kernel: [0] of a built plan. */
+#define NAFP_MELSPEC_ANY_GEOMETRY 1
+#define NAFP_MELSPEC_FORCE_GENERAL 2
+#define NAFP_MELSPEC_PLAN_FIELDS 10
+int nafp_melspec_create_ex(nafp_melspec** plan, int fs, int seg_len, int n_fft, int hop, int n_mels,
+                           float f_min, float f_max, int flags);
+int nafp_melspec_plan_host(int fs, int seg_len, int n_fft, int hop, int n_mels, float f_min, float f_max,
+                           int flags, int64_t* record_host);
+int nafp_melspec_kernel(const nafp_melspec* plan);
 int nafp_melspec_destroy(nafp_melspec* plan);
 int nafp_melspec_n_frames(const nafp_melspec* plan);   /* 1 + seg_len/hop   (32)  */
 int nafp_melspec_n_mels(const nafp_melspec* plan);

@@ -27,6 +27,9 @@ PROTOTYPES = {
     'nafp_crc32c_host': (ctypes.c_uint32, [c_void_p, c_i64, ctypes.c_uint32]),
     'nafp_mel_filterbank_host': (c_int, [c_int, c_int, c_int, c_float, c_float, c_void_p]),
     'nafp_melspec_create': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_float, c_float]),
+    'nafp_melspec_create_ex': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int]),
+    'nafp_melspec_plan_host': (c_int, [c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_void_p]),
+    'nafp_melspec_kernel': (c_int, [c_void_p]),
     'nafp_melspec_destroy': (c_int, [c_void_p]),
     'nafp_melspec_n_frames': (c_int, [c_void_p]),
     'nafp_melspec_n_mels': (c_int, [c_void_p]),

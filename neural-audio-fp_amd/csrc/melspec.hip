@@ -12,7 +12,7 @@
 // bank as a <=8-tap gather from the LDS-resident magnitudes (941 non-zeros in
 // total: never a dense 513x256 GEMM).  The (n_mels, 32) tile is staged in LDS and
 // leaves with 16-byte coalesced stores.
-#include "nafp_common.h"
+#include "melspec_plan.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -24,7 +24,7 @@ constexpr int NFFT = 1024;
 constexpr int HOP = 256;
 constexpr int NBIN = NFFT / 2 + 1;          // 513
 constexpr int MAX_TAPS = 8;
-constexpr int MAX_SEG = 1 << 22;             // LDS use no longer depends on the segment length
+constexpr int MAX_SEG = MELSPEC_MAX_SEG;            // LDS use no longer depends on the segment length
 #ifndef NAFP_MEL_CHUNK
 #define NAFP_MEL_CHUNK 16                    // (8 = twice the workgroups of half the frames: measured, DESIGN.md 4.1 [r4])
 #endif
@@ -34,15 +34,6 @@ constexpr int SIG_CHUNK = (CHUNK_FRAMES - 1) * HOP + NFFT;  // 4864 samples feed
 constexpr int N_TW = 768;                   // twiddles used by the radix-4 passes (index < 3 * 256)
 
 }  // namespace nafp
-
-struct nafp_melspec {
-    int fs, seg_len, n_fft, hop, n_mels, n_frames;
-    float f_min, f_max;
-    float2* d_twiddle;     // 1024: exp(-2 pi i n / 1024)
-    float* d_window;       // 1024 periodic Hann
-    int* d_mel_start;      // n_mels
-    float* d_mel_w;        // n_mels * 8
-};
 
 namespace nafp {
 
@@ -58,8 +49,7 @@ static double mel_to_hz(double m) {
     return m >= min_log_mel ? min_log_hz * std::exp(logstep * (m - min_log_mel)) : f_sp * m;
 }
 
-static void mel_bank_host(int fs, int n_fft, int n_mels, double fmin, double fmax,
-                          std::vector<float>& out) {
+void mel_bank_host(int fs, int n_fft, int n_mels, double fmin, double fmax, std::vector<float>& out) {
     const int n_freq = n_fft / 2 + 1;
     out.assign((size_t)n_mels * n_freq, 0.f);
     std::vector<double> mel_f(n_mels + 2);
@@ -660,6 +650,39 @@ __global__ __launch_bounds__(256) void melspec_finalize_kernel(
     }
 }
 
+// the same for a segment whose n_mels * n_frames is not a multiple of 4 (general geometries only): one element per thread and step
+__global__ __launch_bounds__(256) void melspec_finalize_scalar_kernel(
+        float* __restrict__ feat, const float* __restrict__ group_stat, int64_t n, int64_t per_seg, int group_size, int segment_norm) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t seg = i / per_seg;
+        const int64_t g = group_size > 0 ? seg / group_size : 0;
+        const float gmax = group_stat[2 * g];
+        float v = max_keep_nan(feat[i] - gmax, -80.f);
+        if (segment_norm) {
+            const float mn = fmaxf(group_stat[2 * g + 1] - gmax, -80.f);
+            const float h = mn / 2.f, d = fabsf(h + 1e-10f);
+            v = (v - h) / d;
+        }
+        feat[i] = v;
+    }
+}
+
+static int melspec_finalize(const nafp_melspec* p, float* feat, const float* group_stat, int64_t n_seg, int group_size,
+                            int segment_norm, hipStream_t st) {
+    const int64_t per_seg = (int64_t)p->n_mels * p->n_frames;      // up to 512 * (2^22 + 1) on the general kernel
+    if (per_seg % 4 == 0) {                          // always so for the tuned kernel (n_mels % 64 == 0)
+        const int64_t n_vec4 = n_seg * per_seg / 4;
+        const int blocks = (int)std::min<int64_t>((n_vec4 + 255) / 256, 2048);
+        melspec_finalize_kernel<<<blocks, 256, 0, st>>>(feat, group_stat, n_vec4, (int)(per_seg / 4), group_size, segment_norm);
+    } else {
+        const int64_t n = n_seg * per_seg;
+        const int blocks = (int)std::min<int64_t>((n + 255) / 256, 2048);
+        melspec_finalize_scalar_kernel<<<blocks, 256, 0, st>>>(feat, group_stat, n, per_seg, group_size, segment_norm);
+    }
+    NAFP_LAUNCH_CHECK();
+    return NAFP_OK;
+}
+
 template <typename TIn>
 static int melspec_forward(nafp_melspec* p, const TIn* audio, int64_t n_seg, int group_size,
                            int segment_norm, float* feat, float* group_stat, void* stream,
@@ -674,7 +697,10 @@ static int melspec_forward(nafp_melspec* p, const TIn* audio, int64_t n_seg, int
     // NAFP_MELSPEC_R4=1: the round-1/2 kernel (five in-place radix-4 passes through LDS) for A/B runs
     static const bool r4 = []() { const char* e = getenv("NAFP_MELSPEC_R4"); return e && e[0] == '1'; }();
     const dim3 grid((unsigned)n_seg, (unsigned)((p->n_frames + CHUNK_FRAMES - 1) / CHUNK_FRAMES));
-    if (r4) {
+    if (p->kind == 1) {                          // a plan of nafp_melspec_create_ex on the general kernel (melspec_any.hip)
+        const int rc = launch_melspec_any<TIn>(p, audio, seg_offset, seg_valid, n_seg, group_size, feat, group_stat, st);
+        if (rc != NAFP_OK) return rc;
+    } else if (r4) {
         const size_t lds = (size_t)(SIG_CHUNK + 4 * 2 * NFFT + p->n_mels * TILE_LD + 2 * N_TW) * sizeof(float);
         melspec_kernel<TIn><<<grid, 256, lds, st>>>(audio, seg_offset, seg_valid, feat, group_stat, p->d_twiddle, p->d_window,
                                                     p->d_mel_start, p->d_mel_w, p->seg_len, p->n_frames, p->n_mels, group_size);
@@ -685,15 +711,11 @@ static int melspec_forward(nafp_melspec* p, const TIn* audio, int64_t n_seg, int
     }
     NAFP_LAUNCH_CHECK();
     if (segment_norm & NAFP_MELSPEC_DEFER) return NAFP_OK;   // raw log-mel + group_stat: the consumer finishes
-    segment_norm &= 1;
-    const int per_seg = p->n_mels * p->n_frames;     // multiple of 4 (n_mels % 64 == 0)
-    const int64_t n_vec4 = n_seg * per_seg / 4;
-    const int blocks = (int)std::min<int64_t>((n_vec4 + 255) / 256, 2048);
-    melspec_finalize_kernel<<<blocks, 256, 0, st>>>(feat, group_stat, n_vec4, per_seg / 4,
-                                                    group_size, segment_norm);
-    NAFP_LAUNCH_CHECK();
-    return NAFP_OK;
+    return melspec_finalize(p, feat, group_stat, n_seg, group_size, segment_norm & 1, st);
 }
+
+int melspec_tuned_lds_bytes(int n_mels) { return (SIG_CHUNK + 4 * 2 * R16_BUF + n_mels * TILE_LD + 2 * 64) * (int)sizeof(float); }
+int melspec_tuned_chunk_frames() { return CHUNK_FRAMES; }
 
 }  // namespace nafp
 
@@ -767,6 +789,8 @@ extern "C" int nafp_melspec_destroy(nafp_melspec* p) {
     if (p->d_window) (void)hipFree(p->d_window);
     if (p->d_mel_start) (void)hipFree(p->d_mel_start);
     if (p->d_mel_w) (void)hipFree(p->d_mel_w);
+    if (p->d_mel_cnt) (void)hipFree(p->d_mel_cnt);
+    if (p->d_mel_off) (void)hipFree(p->d_mel_off);
     delete p;
     return NAFP_OK;
 }
@@ -790,13 +814,7 @@ extern "C" int nafp_melspec_finish(nafp_melspec* p, float* feat, const float* gr
     if (!p || !feat || !group_stat || n_seg < 0) return NAFP_ERR_INVALID_ARG;
     if (n_seg == 0) return NAFP_OK;
     if (group_size <= 0 || group_size > n_seg) group_size = (int)std::min<int64_t>(n_seg, INT32_MAX);
-    const int per_seg = p->n_mels * p->n_frames;
-    const int64_t n_vec4 = n_seg * per_seg / 4;
-    const int blocks = (int)std::min<int64_t>((n_vec4 + 255) / 256, 2048);
-    melspec_finalize_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(feat, group_stat, n_vec4, per_seg / 4, group_size,
-                                                                     segment_norm & 1);
-    NAFP_LAUNCH_CHECK();
-    return NAFP_OK;
+    return melspec_finalize(p, feat, group_stat, n_seg, group_size, segment_norm & 1, (hipStream_t)stream);
 }
 
 extern "C" int nafp_melspec_forward_windows_i16(nafp_melspec* plan, const int16_t* pcm, const int64_t* seg_offset,

@@ -11,8 +11,17 @@ the max over the whole device batch (melspectrogram.py:108), and its batches are
 `TS_BATCH_SZ` consecutive segments; here a launch may hold several such batches,
 so the grouping is a parameter (None = the whole input is one group, exactly the
 reference's behaviour for one batch).
+
+Geometry: the tuned kernel serves STFT_WIN 1024 / STFT_HOP 256 with banks of filters up to 8 bins wide, and that is all the
+layer builds by default.  With NAFP_MELSPEC_ANY=1 in the environment every other value of MODEL.FS / STFT_WIN / STFT_HOP /
+N_MELS / F_MIN / F_MAX / DUR inside the general kernel's range (include/nafp.h, nafp_melspec_create_ex) is built as well; the
+layer says so once on stderr.  `Melspec_layer.front_end` describes what was built.
 """
 import ctypes
+import os
+import sys
+
+import numpy as np
 
 import torch
 
@@ -39,6 +48,16 @@ class DeferredFeatures:
         return out
 
 
+ANY_GEOMETRY, FORCE_GENERAL = 1, 2        # NAFP_MELSPEC_ANY_GEOMETRY, NAFP_MELSPEC_FORCE_GENERAL (include/nafp.h)
+PLAN_FIELDS = ('kernel', 'n_frames', 'n_bins', 'bank_nonzeros', 'widest_filter', 'empty_filters', 'frames_per_workgroup',
+               'lds_bytes', 'workgroups_per_segment', 'frame_pairs_in_flight')
+_announced = set()
+
+
+def any_geometry_enabled():
+    return os.environ.get('NAFP_MELSPEC_ANY', '') == '1'
+
+
 class Melspec_layer:
     def __init__(self, input_shape=(1, 8000), segment_norm=False, n_fft=1024, stft_hop=256,
                  n_mels=256, fs=8000, dur=1., f_min=300., f_max=4000., amin=1e-10,
@@ -57,13 +76,44 @@ class Melspec_layer:
         self.seg_len = int(input_shape[1])
         self.padded_input_shape = (1, int(fs * dur) + self.pad_l + self.pad_r)
         self.group_size = kwargs.pop('group_size', None)
+        # `plan_flags` (tests, A/B runs): the flags of nafp_melspec_create_ex; None = what the environment asks for
+        flags = kwargs.pop('plan_flags', None)
+        if flags is None:
+            flags = ANY_GEOMETRY if any_geometry_enabled() else 0
         lib = _lib.load()
         h = ctypes.c_void_p()
-        _lib.check(lib.nafp_melspec_create(ctypes.byref(h), int(fs), self.seg_len, int(n_fft),
-                                           int(stft_hop), int(n_mels), float(f_min), float(f_max)),
-                   'melspec_create')
+        geom = (int(fs), self.seg_len, int(n_fft), int(stft_hop), int(n_mels), float(f_min), float(f_max))
+        if flags:
+            rc = lib.nafp_melspec_create_ex(ctypes.byref(h), *geom, int(flags))
+        else:
+            rc = lib.nafp_melspec_create(ctypes.byref(h), *geom)
+        if rc == 2 and not flags:
+            raise _lib.NafpError(f'libnafp melspec_create: {lib.nafp_status_string(rc).decode()}: fs, seg_len, n_fft, hop, n_mels, '
+                                 f'f_min, f_max = {geom} is outside the tuned front end (n_fft 1024, hop 256, filters <= 8 bins '
+                                 'wide); NAFP_MELSPEC_ANY=1 builds the general kernel for it')
+        _lib.check(rc, 'melspec_create')
         self._h, self._lib = h, lib
         self.n_frames = lib.nafp_melspec_n_frames(h)
+        self.kernel = int(lib.nafp_melspec_kernel(h))                    # 0 tuned, 1 general
+        self._geom, self._flags, self._front_end = geom, int(flags), None
+        if self.kernel == 1 and geom not in _announced:
+            _announced.add(geom)
+            print(f'[nafp] log-mel front end on the general kernel: fs {geom[0]}, seg_len {geom[1]}, n_fft {geom[2]}, hop {geom[3]}, '
+                  f'n_mels {geom[4]}, f_min {geom[5]:g}, f_max {geom[6]:g} -> ({geom[4]}, {self.n_frames}) per segment, '
+                  f'{self.front_end["lds_bytes"]} B LDS per workgroup', file=sys.stderr, flush=True)
+
+    @property
+    def front_end(self):
+        """The geometry and the plan record (include/nafp.h, nafp_melspec_plan_host) of what was built; worked out on first use."""
+        if self._front_end is None:
+            geom = self._geom
+            rec = np.zeros(len(PLAN_FIELDS), np.int64)
+            _lib.check(self._lib.nafp_melspec_plan_host(*geom, self._flags, rec.ctypes.data_as(ctypes.c_void_p)), 'melspec_plan_host')
+            fe = {'fs': geom[0], 'seg_len': geom[1], 'n_fft': geom[2], 'hop': geom[3], 'n_mels': geom[4], 'f_min': geom[5],
+                  'f_max': geom[6], 'segment_norm': bool(self.segment_norm), 'kernel_name': 'general' if self.kernel == 1 else 'tuned'}
+            fe.update({k: int(v) for k, v in zip(PLAN_FIELDS, rec)})
+            self._front_end = fe
+        return self._front_end
 
     def __del__(self):
         h = getattr(self, '_h', None)

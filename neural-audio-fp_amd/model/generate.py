@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from .dataset import Dataset
-from .fp.melspec.melspectrogram import get_melspec_layer
+from .fp.melspec.melspectrogram import any_geometry_enabled, get_melspec_layer
 from .fp.nnfp import get_fingerprinter
 
 LAUNCH_SEGMENTS = 640       # target segments per launch (whole groups)
@@ -454,6 +454,10 @@ def generate_fingerprint(cfg, checkpoint_name, checkpoint_index, source_root_dir
         import json
         with open(f'{output_root_dir}/source_rates.json', 'w') as f:
             json.dump(source_rates, f, indent=1, sort_keys=True)
+    if rank == 0 and any_geometry_enabled():   # NAFP_MELSPEC_ANY=1: the front end's geometry and kernel, next to the .mm files
+        import json
+        with open(f'{output_root_dir}/front_end.json', 'w') as f:
+            json.dump(m_pre.front_end, f, indent=1, sort_keys=True)
     if 'custom_source' in ds.keys():
         pass
     elif sz_check['db'] != sz_check['query']:

@@ -196,6 +196,86 @@ int nafp_resample_i16(nafp_resample* plan, const int16_t* raw, int64_t raw_sampl
                       void* stream);
 
 /* ------------------------------------------------------------------------
+ * Ingest of any PCM / IEEE-float WAV, 1 to 8 channels, at any supported rate in EITHER direction (csrc/ingest.hip; numpy
+ * restatement tests/_ingest_ref.py).  The general sibling of nafp_resample_*, which is unchanged;
+ * for 16-bit files with 1 or 2 channels at a higher rate the two write the same bytes.  EXACT INTEGER ARITHMETIC: an output
+ * sample is a pure function of (file bytes, output index), whatever shares its piece, block or launch.
+ *
+ * Canonical sample q: a signed integer at 2^-23 of full scale, |q| <= 2^23, from the little-endian sample as the file holds it
+ * (for WAVE_FORMAT_EXTENSIBLE the container of block_align / channels bytes: samples are MSB-justified in it):
+ *   NAFP_INGEST_U8   unsigned 8-bit PCM       q = (u - 128) << 16
+ *   NAFP_INGEST_S16  16-bit PCM               q = x << 8
+ *   NAFP_INGEST_S24  24-bit PCM, 3 bytes      q = x (sign-extended)
+ *   NAFP_INGEST_S32  32-bit PCM               q = min((x + 128) >> 8, 2^23 - 1), arithmetic shift, the sum formed in 64 bits
+ *   NAFP_INGEST_F32 / NAFP_INGEST_F64  IEEE   NaN -> 0; otherwise q = clamp(rint(x * 2^23), -2^23, 2^23 - 1), ties to even, the
+ *                                             clamp applied before the conversion to integer (infinities clamp, denormals give
+ *                                             0); computed from the bit pattern in integers on host and device alike
+ * Down-mix: m[j] = sum_c q[j][c] over the C = 1..8 channels of frame j, equal weights; the division by C is part of the
+ * final rounding.
+ * Ratio: g = gcd(fs_in, fs_out), L = fs_out / g, M = fs_in / g.  Supported: both rates <= 192000 and L <= 640, in either
+ * direction (11025 -> 16000 is L = 640, M = 441), provided the input span of a 256-output block,
+ * ceil(255 M / L) + T + 1 int32, fits 64 KB of LDS (otherwise NAFP_ERR_UNSUPPORTED from every entry point, plan creation
+ * included); fs_in == fs_out is the identity geometry L = M = 1, half = 0, T = 1, the single tap 2^30.
+ * Filter: nafp_resample_*'s design with the LOWER of the two rates in the place of fs_out: lo = min(fs_in, fs_out),
+ * fv = fs_in * L, fc = 0.95 lo / 2, half = ceil(640 fv / (19 lo)),
+ *   h[v]  = sinc(2 fc v / fv) * I0(8.6 sqrt(1 - (v / half)^2)) / I0(8.6) * (2 fc / fv) * L,   v in [-half, half]
+ *   hq[v] = round(h[v] * 2^30) as int32,   T = ceil((2 half + 1) / L) taps per phase.
+ * For fs_in > fs_out this is nafp_resample_table_host's table bit for bit.  Per phase sum |hq| / 2^30 < 2.5.
+ * Output: n_out = ceil(n_in * L / M); samples outside the file are zero;
+ *   acc[n] = sum_j hq[n M - j L] * m[j]  over |n M - j L| <= half     (exact in int64: |acc| <= 2^23 * 8 * 2.5 * 2^30 < 2^58)
+ *   y[n]   = clamp(floor((acc[n] + D / 2) / D), -32768, 32767),   D = C * 2^38, floor division.
+ * Status: a ratio, format or channel count outside the list NAFP_ERR_UNSUPPORTED, null pointers / negative sizes / an
+ * inconsistent piece NAFP_ERR_INVALID_ARG, all before any GPU call.
+ * ---------------------------------------------------------------------- */
+typedef struct nafp_ingest nafp_ingest;
+
+#define NAFP_INGEST_U8 1
+#define NAFP_INGEST_S16 2
+#define NAFP_INGEST_S24 3
+#define NAFP_INGEST_S32 4
+#define NAFP_INGEST_F32 5
+#define NAFP_INGEST_F64 6
+
+/* A run of consecutive output samples of one file: nafp_resample_piece with a BYTE offset into a uint8 arena (any
+ * alignment), a format code and 1..8 channels.  64 bytes. */
+typedef struct nafp_ingest_piece {
+    int64_t raw_off;     /* byte index in the raw arena of the first uploaded frame (frames interleaved as in the file) */
+    int64_t frame0;      /* which frame of the file that is */
+    int64_t n_frames;    /* frames uploaded */
+    int64_t n_in;        /* frames of the whole file */
+    int64_t out0;        /* index in the file's output stream of the first output */
+    int64_t out_off;     /* int16 index in the output arena of that output */
+    int32_t n_out;       /* outputs */
+    int32_t channels;    /* 1 .. 8 */
+    int32_t format;      /* NAFP_INGEST_* */
+    int32_t reserved;
+} nafp_ingest_piece;
+
+/* Host only. */
+int nafp_ingest_geometry(int fs_in, int fs_out, int* L, int* M, int* half, int* T);
+/* Host only: the canonical table (L, T) int32, [phase p][tap t] = hq[p + t L - half], as nafp_resample_table_host. */
+int nafp_ingest_table_host(int fs_in, int fs_out, int32_t* table_host);
+int64_t nafp_ingest_n_out(int64_t n_in, int fs_in, int fs_out);            /* -1: unsupported ratio / negative n_in */
+/* Host only: the frames [*first, *last) of a file of n_in frames that the outputs [n0, n1) read (first == last: none). */
+int nafp_ingest_input_range(int64_t n0, int64_t n1, int64_t n_in, int fs_in, int fs_out, int64_t* first, int64_t* last);
+/* Host only: q of n_samples consecutive samples of `format` at `bytes` (any alignment) -- the function the kernel decodes
+ * with, compiled for the host. */
+int nafp_ingest_decode_host(int format, const void* bytes, int64_t n_samples, int32_t* q_out);
+/* Host only: the checks the kernel makes per piece.  NAFP_ERR_INVALID_ARG for an inconsistent piece, NAFP_ERR_UNSUPPORTED
+ * for a format code or a channel count outside the contract. */
+int nafp_ingest_check_pieces_host(int fs_in, int fs_out, const nafp_ingest_piece* pieces_host, int64_t n_pieces,
+                                  int64_t raw_size, int64_t out_samples);
+/* The plan owns the device table. */
+int nafp_ingest_create(nafp_ingest** plan, int fs_in, int fs_out);
+int nafp_ingest_destroy(nafp_ingest* plan);
+/* raw_bytes (raw_size bytes) -> out (out_samples int16) for the n_pieces pieces of pieces_dev, all device pointers.  Every
+ * index derived from a piece is checked on the device against raw_size / out_samples: an inconsistent piece is skipped, its
+ * outputs zeroed (nothing is written for one whose output range leaves the arena).  No byte outside the two arenas is read
+ * or written whatever a piece says; int16 outside the pieces' output ranges is not touched. */
+int nafp_ingest_i16(nafp_ingest* plan, const uint8_t* raw_bytes, int64_t raw_size, const nafp_ingest_piece* pieces_dev,
+                    int64_t n_pieces, int16_t* out, int64_t out_samples, void* stream);
+
+/* ------------------------------------------------------------------------
  * Encoder: FingerPrinter (model/fp/nnfp.py:159-231)
  * ---------------------------------------------------------------------- */
 

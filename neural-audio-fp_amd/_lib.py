@@ -47,6 +47,16 @@ PROTOTYPES = {
     'nafp_resample_create': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int]),
     'nafp_resample_destroy': (c_int, [c_void_p]),
     'nafp_resample_i16': (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p]),
+    'nafp_ingest_geometry': (c_int, [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                     ctypes.POINTER(c_int)]),
+    'nafp_ingest_table_host': (c_int, [c_int, c_int, c_void_p]),
+    'nafp_ingest_n_out': (c_i64, [c_i64, c_int, c_int]),
+    'nafp_ingest_input_range': (c_int, [c_i64, c_i64, c_i64, c_int, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    'nafp_ingest_decode_host': (c_int, [c_int, c_void_p, c_i64, c_void_p]),
+    'nafp_ingest_check_pieces_host': (c_int, [c_int, c_int, c_void_p, c_i64, c_i64, c_i64]),
+    'nafp_ingest_create': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int]),
+    'nafp_ingest_destroy': (c_int, [c_void_p]),
+    'nafp_ingest_i16': (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p]),
     'nafp_encoder_create': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int]),
     'nafp_encoder_create_ex': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int]),
     'nafp_encoder_norm': (c_int, [c_void_p]),
@@ -171,6 +181,13 @@ AUG_ROW_DTYPE = [('ev_off', '<i8'), ('nz_off', '<i8'), ('nz2_off', '<i8'), ('ir_
 # nafp_resample_piece (include/nafp.h) as a numpy structured dtype: 56 bytes per piece
 RESAMPLE_PIECE_DTYPE = [('raw_off', '<i8'), ('frame0', '<i8'), ('n_frames', '<i8'), ('n_in', '<i8'), ('out0', '<i8'),
                         ('out_off', '<i8'), ('n_out', '<i4'), ('channels', '<i4')]
+
+
+# nafp_ingest_piece (include/nafp.h) as a numpy structured dtype: 64 bytes per piece; raw_off counts BYTES
+INGEST_PIECE_DTYPE = [('raw_off', '<i8'), ('frame0', '<i8'), ('n_frames', '<i8'), ('n_in', '<i8'), ('out0', '<i8'),
+                      ('out_off', '<i8'), ('n_out', '<i4'), ('channels', '<i4'), ('format', '<i4'), ('reserved', '<i4')]
+# NAFP_INGEST_* format codes (include/nafp.h): name -> (code, bytes per sample)
+INGEST_FORMATS = {'u8': (1, 1), 's16': (2, 2), 's24': (3, 3), 's32': (4, 4), 'f32': (5, 4), 'f64': (6, 8)}
 
 
 class NafpError(RuntimeError):

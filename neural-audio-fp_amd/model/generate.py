@@ -437,7 +437,13 @@ def generate_fingerprint(cfg, checkpoint_name, checkpoint_index, source_root_dir
         if rank != 0:
             arr = np.memmap(path, dtype='float32', mode='r+', shape=arr_shape)
         print(f"=== Generating fingerprint from \x1b[1;32m'{key}'\x1b[0m bsz={bsz}, {n_items} items, d={dim} ===")
-        if getattr(ds[key], 'resample', False):
+        files = getattr(ds[key], 'ev', ds[key])    # a synthesising sequence ('unseen_syn'): the store of its event files
+        if getattr(files, 'ingest', False):        # NAFP_INGEST_ANY=1: any PCM / float format, channel count and rate
+            from .utils.ingest import rates_summary
+            source_rates[key] = rates_summary(files)
+            print(f"'{key}': {source_rates[key]['resampled']} of {source_rates[key]['files']} files are decoded, mixed down and "
+                  f"resampled to {files.fs} Hz 16-bit mono on the device (rate x channels x format: files) {source_rates[key]['rates']}")
+        elif getattr(ds[key], 'resample', False):
             from .utils.resample import rates_summary
             source_rates[key] = rates_summary(ds[key])
             print(f"'{key}': {source_rates[key]['resampled']} of {source_rates[key]['files']} files are resampled to "

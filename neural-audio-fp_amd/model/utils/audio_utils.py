@@ -57,6 +57,80 @@ def riff_scan(filename):
                 f.seek(csz + (csz & 1), 1)
 
 
+_WAVE_TAGS = {0x0002: 'ADPCM', 0x0006: 'A-law', 0x0007: 'mu-law', 0x0011: 'IMA ADPCM', 0x0031: 'GSM 6.10', 0x0050: 'MPEG',
+              0x0055: 'MPEG layer 3'}
+_GUID_TAIL = bytes.fromhex('000000001000800000aa00389b71')          # KSDATAFORMAT_SUBTYPE_*: the tag as 2 bytes, then this
+_PCM_WIDTHS = {1: 'u8', 2: 's16', 3: 's24', 4: 's32'}
+_FLOAT_WIDTHS = {4: 'f32', 8: 'f64'}
+
+
+def riff_scan_ex(filename, fs=None):
+    """Header scan of a RIFF/WAVE file for the general ingest (NAFP_INGEST_ANY=1, utils/ingest.py), WITHOUT reading the samples:
+    {'rate', 'channels', 'format' ('u8' | 's16' | 's24' | 's32' | 'f32' | 'f64'), 'width' (bytes per sample in the file),
+    'block_align', 'offset' (byte offset of the first sample), 'n_frames'}.
+    Taken: format tag 1 (PCM) at 8 / 16 / 24 / 32 bits, tag 3 (IEEE float) at 32 / 64 bits, and tag 0xFFFE (extensible) whose
+    sub-format GUID is the PCM or the IEEE-float one -- there the container width is block_align / channels (samples are
+    MSB-justified in it, so wValidBitsPerSample is not needed); 1 to 8 channels; block_align == channels * width.  Everything
+    else raises ValueError by name, and with `fs` given so does a rate that cannot be brought to fs, in the reference's wording
+    (audio_utils.py:160-169)."""
+    size = os.path.getsize(filename)
+    with open(filename, 'rb') as f:
+        head = f.read(12)
+        if len(head) < 12 or head[:4] != b'RIFF' or head[8:12] != b'WAVE':
+            raise ValueError(f'{filename}: not a RIFF/WAVE file')
+        fmt = None
+        while True:
+            hdr = f.read(8)
+            if len(hdr) < 8:
+                raise ValueError(f'{filename}: no data chunk')
+            cid, csz = hdr[:4], struct.unpack('<I', hdr[4:])[0]
+            if cid == b'fmt ':
+                fmt = f.read(csz + (csz & 1))[:csz]
+                if len(fmt) < 16:
+                    raise ValueError(f'{filename}: fmt chunk of {len(fmt)} bytes')
+            elif cid == b'data':
+                if fmt is None:
+                    raise ValueError(f'{filename}: data chunk before fmt chunk')
+                off = f.tell()
+                csz = min(csz, size - off)
+                break
+            else:
+                f.seek(csz + (csz & 1), 1)
+    tag, ch, rate, _, align, bits = struct.unpack('<HHIIHH', fmt[:16])
+    if ch < 1 or ch > 8:
+        raise ValueError(f'{filename}: {ch} channels; 1 to 8 are taken')
+    if tag == 0xFFFE:
+        if len(fmt) < 40:
+            raise ValueError(f'{filename}: extensible fmt chunk of {len(fmt)} bytes')
+        guid = fmt[24:40]
+        if guid[2:] != _GUID_TAIL or guid[:2] not in (b'\x01\x00', b'\x03\x00'):
+            raise ValueError(f'{filename}: extensible header with unknown sub-format GUID {guid.hex()}; taken: PCM, IEEE float')
+        kind = guid[0]
+        if align % ch:
+            raise ValueError(f'{filename}: block_align {align} is not a multiple of {ch} channels')
+        width = align // ch
+    elif tag in (1, 3):
+        kind = tag
+        if bits % 8:
+            raise ValueError(f'{filename}: {bits}-bit samples; taken: PCM at 8 / 16 / 24 / 32 bits, IEEE float at 32 / 64')
+        width = bits // 8
+    else:
+        name = _WAVE_TAGS.get(tag)
+        raise ValueError(f'{filename}: WAVE format tag 0x{tag:04x}' + (f' ({name})' if name else '') +
+                         ' is not taken; taken: PCM (1), IEEE float (3), extensible (0xfffe) holding either')
+    name = (_PCM_WIDTHS if kind == 1 else _FLOAT_WIDTHS).get(width)
+    if name is None:
+        raise ValueError(f'{filename}: {8 * width}-bit {"PCM" if kind == 1 else "IEEE float"} samples; taken: PCM at 8 / 16 / 24 / 32 '
+                         f'bits, IEEE float at 32 / 64')
+    if align != ch * width:
+        raise ValueError(f'{filename}: block_align {align} != {ch} channels * {width} bytes per sample')
+    if fs is not None:
+        from . import ingest as ig
+        ig.check_rate(rate, fs)
+    return {'rate': rate, 'channels': ch, 'format': name, 'width': width, 'block_align': align, 'offset': off,
+            'n_frames': csz // align}
+
+
 def wav_info(filename, fs):
     """Frame count of a 16-bit mono WAV; ValueError on a wrong sample rate
     (audio_utils.py:160-169)."""
@@ -102,6 +176,10 @@ def _resample_on():
     return os.environ.get('NAFP_RESAMPLE', '') == '1'
 
 
+def _ingest_on():
+    return os.environ.get('NAFP_INGEST_ANY', '') == '1'
+
+
 class SegmentSource:
     """Ordered segments of a list of WAV files, served in consecutive batches.
 
@@ -118,11 +196,25 @@ class SegmentSource:
         self.n_frames, self.data_offset = [], []
         # NAFP_RESAMPLE=1: files at other rates / in stereo are taken too and resampled on the device (utils/resample.py);
         # n_frames is then the length at the model rate, n_in / rate / channels describe the file itself
-        self.resample = _resample_on()
+        # NAFP_INGEST_ANY=1 (includes the above): any PCM / float format, 1 to 8 channels, rates in either direction
+        # (utils/ingest.py); `format` / `block_align` then describe the file's samples, and the raw arena of a launch holds BYTES
+        self.ingest = _ingest_on()
+        self.resample = _resample_on() or self.ingest
         self.rate, self.channels, self.n_in, self.resampled = [], [], [], []
+        self.format, self.block_align = [], []
         for fn in self.fns:                      # ONE header scan per file (the reference re-opens per segment)
             if fn[-3:] != 'wav':
                 raise NotImplementedError(fn[-3:])
+            if self.ingest:
+                from . import ingest as ig
+                info = riff_scan_ex(fn, fs)
+                rate, ch, off, nfr = info['rate'], info['channels'], info['offset'], info['n_frames']
+                native = ig.is_native(info, fs)
+                n_model = nfr if native else ig.n_out(nfr, rate, fs)
+                self.format.append(info['format']); self.block_align.append(info['block_align'])
+                self.n_frames.append(n_model); self.data_offset.append(off)
+                self.rate.append(rate); self.channels.append(ch); self.n_in.append(nfr); self.resampled.append(not native)
+                continue
             rate, ch, width, off, nfr = riff_scan(fn)
             if self.resample:
                 from . import resample as rs
@@ -145,6 +237,10 @@ class SegmentSource:
         return (self.n_samples + self.bsz - 1) // self.bsz
 
     def _host_pcm(self, f):
+        if self.resampled[f] and self.ingest:
+            raise NotImplementedError(f'{self.fns[f]}: {self.rate[f]} Hz x {self.channels[f]} x {self.format[f]} is decoded and '
+                                      'resampled on the device only (iter_windows + StreamedEmbedder.embed_windows); there is no '
+                                      'CPU path')
         if self.resampled[f]:
             raise NotImplementedError(f'{self.fns[f]}: {self.rate[f]} Hz x {self.channels[f]} is resampled on the device only '
                                       '(iter_windows + StreamedEmbedder.embed_windows); there is no CPU resampler')
@@ -191,7 +287,8 @@ class SegmentSource:
 
     def iter_windows(self, row0, row1, rows_per_chunk, alloc=None):
         """Yield (start_row, n_rows, arena, used, seg_offset, seg_valid) -- with NAFP_RESAMPLE=1 a seventh item, the launch's
-        resampling work (utils/resample.ChunkPieces) or None for a launch of model-rate mono files -- over rows [row0, row1):
+        resampling work (utils/resample.ChunkPieces; with NAFP_INGEST_ANY=1 utils/ingest.ChunkPieces, the arena then holding the
+        files' bytes) or None for a launch of model-rate mono files -- over rows [row0, row1):
         the PCM every row needs is read ONCE from each file (contiguous sample range, straight into
         `arena` = alloc(n_samples), e.g. pinned memory) and row i is the window
         arena[seg_offset[i] : seg_offset[i] + seg_len] with samples >= seg_valid[i] meaning zero --
@@ -212,7 +309,8 @@ class SegmentSource:
                 total += (s1 - s0 + 7) // 8 * 8                      # 16-B aligned piece starts
                 q += b - a
             if self.resample and any(self.resampled[p[0]] for p in pieces):
-                yield (r, n) + self._resample_chunk(pieces, n, total, alloc)
+                chunk = self._ingest_chunk if self.ingest else self._resample_chunk
+                yield (r, n) + chunk(pieces, n, total, alloc)
                 r = end
                 continue
             arena = alloc(total) if alloc is not None else np.empty(max(total, 1), np.int16)
@@ -265,3 +363,36 @@ class SegmentSource:
             seg_valid[o:o + (b - a)] = np.clip(self.n_frames[f] - k * hop_len, 0, seg_len)
         by_rate = {rate: np.array(rows, dtype=rs.PIECE_DTYPE) for rate, rows in by_rate.items()}
         return arena, raw_total, seg_offset, seg_valid, rs.ChunkPieces(self.fs, by_rate, total)
+
+    def _ingest_chunk(self, pieces, n, total, alloc):
+        """`_resample_chunk` for NAFP_INGEST_ANY=1: (raw arena, used, seg_offset, seg_valid, ingest.ChunkPieces).  `arena` (int16
+        units, as `alloc` hands it out; `used` counts them) holds the files' BYTES: for every piece the byte range
+        nafp_ingest_input_range x block_align, read as the file has it, piece starts 16-B aligned.  seg_offset / seg_valid index
+        the model-rate arena of `total` samples, unchanged.  Native files go the same way in such a launch (identity plan)."""
+        from . import ingest as ig
+        seg_len, hop_len = self.seg_len, self.hop_len
+        raw_bytes, spans = 0, []
+        for f, a, b, s0, s1, base, o in pieces:
+            first, last = ig.input_range(s0, s1, self.n_in[f], self.rate[f], self.fs) if s1 > s0 else (0, 0)
+            spans.append((first, last, raw_bytes))
+            raw_bytes += ((last - first) * self.block_align[f] + 15) // 16 * 16
+        used = raw_bytes // 2
+        arena = alloc(used) if alloc is not None else np.empty(max(used, 1), np.int16)
+        raw = arena.view(np.uint8)
+        seg_offset = np.empty(n, np.int64)
+        seg_valid = np.empty(n, np.int32)
+        by_rate = {}
+        for (f, a, b, s0, s1, base, o), (first, last, raw_base) in zip(pieces, spans):
+            align = self.block_align[f]
+            if last > first:
+                with open(self.fns[f], 'rb', buffering=0) as fh:
+                    fh.seek(self.data_offset[f] + align * first)
+                    if fh.readinto(memoryview(raw[raw_base:raw_base + (last - first) * align])) != align * (last - first):
+                        raise IOError(f'{self.fns[f]}: short read')
+            by_rate.setdefault(self.rate[f], []).append((raw_base, first, last - first, self.n_in[f], s0, base, s1 - s0,
+                                                         self.channels[f], ig.FORMATS[self.format[f]][0], 0))
+            k = np.arange(a, b, dtype=np.int64)
+            seg_offset[o:o + (b - a)] = base + (k - a) * hop_len
+            seg_valid[o:o + (b - a)] = np.clip(self.n_frames[f] - k * hop_len, 0, seg_len)
+        by_rate = {rate: np.array(rows, dtype=ig.PIECE_DTYPE) for rate, rows in by_rate.items()}
+        return arena, used, seg_offset, seg_valid, ig.ChunkPieces(self.fs, by_rate, total)

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from ... import _lib
-from .audio_utils import n_segments, riff_scan, _resample_on
+from .audio_utils import n_segments, riff_scan, riff_scan_ex, _resample_on, _ingest_on
 
 MAX_IR_LENGTH = 600          # dataloader_keras.py:8
 
@@ -61,12 +61,26 @@ class PcmStore:
     def __init__(self, fns, fs, base=0):
         self.fns, self.fs = list(fns), fs
         self.n_frames, self.data_offset, self.start = [], [], []
-        self.resample = _resample_on()
+        # NAFP_INGEST_ANY=1 (includes NAFP_RESAMPLE=1): any PCM / float format, 1 to 8 channels, rates in either direction
+        self.ingest = _ingest_on()
+        self.resample = _resample_on() or self.ingest
         self.rate, self.channels, self.n_in, self.resampled = [], [], [], []
+        self.format, self.block_align = [], []
         pos = int(base)
         for fn in self.fns:
             if fn[-3:] != 'wav':
                 raise NotImplementedError(fn[-3:])
+            if self.ingest:
+                from . import ingest as ig
+                info = riff_scan_ex(fn, fs)
+                rate, ch, off, nfr = info['rate'], info['channels'], info['offset'], info['n_frames']
+                native = ig.is_native(info, fs)
+                n_model = nfr if native else ig.n_out(nfr, rate, fs)
+                self.format.append(info['format']); self.block_align.append(info['block_align'])
+                self.n_frames.append(n_model); self.data_offset.append(off); self.start.append(pos)
+                self.rate.append(rate); self.channels.append(ch); self.n_in.append(nfr); self.resampled.append(not native)
+                pos += (n_model + 7) // 8 * 8
+                continue
             rate, ch, width, off, nfr = riff_scan(fn)
             if self.resample:
                 from . import resample as rs
@@ -90,6 +104,9 @@ class PcmStore:
         """dst: int16 numpy view of [base, end) (zero-initialised by the caller)."""
         for f, fn in enumerate(self.fns):
             n = int(self.n_frames[f])
+            if self.resampled[f] and getattr(self, 'ingest', False):
+                raise NotImplementedError(f'{fn}: {self.rate[f]} Hz x {self.channels[f]} x {self.format[f]} is decoded and resampled '
+                                          'on the device only (PcmArena.device); there is no CPU path')
             if self.resampled[f]:
                 raise NotImplementedError(f'{fn}: {self.rate[f]} Hz x {self.channels[f]} is resampled on the device only '
                                           '(PcmArena.device); there is no CPU resampler')
@@ -143,7 +160,7 @@ class PcmArena:
                 f = g
             for f in range(len(s.fns)):
                 if s.resampled[f]:
-                    self._resample_file(s, f, d, stage)
+                    (self._ingest_file if s.ingest else self._resample_file)(s, f, d, stage)
         if any(any(s.resampled) for s in self.stores):
             torch.cuda.current_stream(device).synchronize()
         return d
@@ -172,6 +189,34 @@ class PcmArena:
                         raise IOError(f'{s.fns[f]}: short read')
                 raw = stage[:max(k, 1)].to(d.device, non_blocking=False)
                 piece = np.array([(0, first, last - first, n_in, n0, start + n0, n1 - n0, ch)], dtype=rs.PIECE_DTYPE)
+                plan.run(raw, piece, d)
+
+    @staticmethod
+    def _ingest_file(s, f, d, stage):
+        """`_resample_file` for NAFP_INGEST_ANY=1: the file's BYTES go through the staging buffer in runs of outputs (each run
+        uploads the byte range nafp_ingest_input_range x block_align) and one nafp_ingest_piece per run."""
+        from . import ingest as ig
+        plan = ig.plan_for(s.rate[f], s.fs, d.device)
+        align, n_in, n_total, start = int(s.block_align[f]), int(s.n_in[f]), int(s.n_frames[f]), int(s.start[f])
+        fmt = ig.FORMATS[s.format[f]][0]
+        stage_bytes = stage.numpy().view(np.uint8)
+        # outputs per run: their input span (n M / L frames + the filter's two half-widths) fits the staging buffer
+        margin = 2 * (plan.half // plan.L + 2)
+        room = len(stage_bytes) // align - margin
+        if room * plan.L < plan.M:
+            raise NotImplementedError(f'{s.fns[f]}: staging buffer too small to convert from {s.rate[f]} Hz')
+        step = max(1, min(room * plan.L // plan.M, (1 << 31) - 1))
+        with open(s.fns[f], 'rb', buffering=0) as fh:
+            for n0 in range(0, n_total, step):
+                n1 = min(n_total, n0 + step)
+                first, last = ig.input_range(n0, n1, n_in, s.rate[f], s.fs)
+                k = (last - first) * align
+                if k:
+                    fh.seek(s.data_offset[f] + align * first)
+                    if fh.readinto(memoryview(stage_bytes[:k])) != k:
+                        raise IOError(f'{s.fns[f]}: short read')
+                raw = stage[:max((k + 1) // 2, 1)].to(d.device, non_blocking=False).view(torch.uint8)
+                piece = np.array([(0, first, last - first, n_in, n0, start + n0, n1 - n0, s.channels[f], fmt, 0)], dtype=ig.PIECE_DTYPE)
                 plan.run(raw, piece, d)
 
 

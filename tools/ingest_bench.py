@@ -1,0 +1,133 @@
+"""Kernel cost of the general ingest (NAFP_INGEST_ANY=1, csrc/ingest.hip) for one generate launch of 640 segments.
+
+    python tools/ingest_bench.py [reps=7] [launches_per_rep=20]
+
+Device-event times, every shape warmed up first, `reps` windows of `launches_per_rep` launches each per case, the cases
+alternating inside a rep so that drift hits them alike; median and range over the reps, per launch:
+  1. the one class of input both kernels serve, 16-bit stereo at 44.1 kHz: nafp_ingest_i16 next to nafp_resample_i16 on the same
+     samples and pieces (outputs compared byte for byte on the way), and their ratio;
+  2. 24-bit stereo at 48 kHz -> 8 kHz and 16-bit mono 11.025 kHz -> 16 kHz, next to the log-mel kernel of the same launch
+     (640 windows over the ingest's output; the 16 kHz front end needs NAFP_MELSPEC_ANY=1, which this tool sets for that case).
+A launch is 640 one-second segments at a hop of 0.5 s: 320.5 s of audio, cut into 30-s files as generate would (11 pieces).
+One JSON line at the end."""
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+args = [a for a in sys.argv[1:] if not a.startswith('--')]
+REPS = int(args[0]) if args else 7
+PER_REP = int(args[1]) if len(args) > 1 else 20
+SEGMENTS, FILE_SECONDS = 640, 30
+
+
+def pieces_for(mod, fs_in, fs_out, frame_bytes, unit, extra):
+    """The launch as generate cuts it: consecutive 30-s files, each one piece; raw offsets in `unit`-byte units (1: the ingest's
+    bytes, 2: the resampler's int16), 16-byte aligned.  -> (piece array, raw bytes, outputs)."""
+    total_out = (SEGMENTS - 1) * (fs_out // 2) + fs_out
+    rows, raw_pos, out_pos = [], 0, 0
+    while out_pos < total_out:
+        n_in = FILE_SECONDS * fs_in
+        n_out = min(mod.n_out(n_in, fs_in, fs_out), total_out - out_pos)
+        first, last = mod.input_range(0, n_out, n_in, fs_in, fs_out)
+        rows.append((raw_pos // unit, first, last - first, n_in, 0, out_pos, n_out) + extra)
+        raw_pos += ((last - first) * frame_bytes + 15) // 16 * 16
+        out_pos += (n_out + 7) // 8 * 8
+    return np.array(rows, dtype=mod.PIECE_DTYPE), raw_pos, out_pos
+
+
+def timed(fns):
+    """Per-launch milliseconds of each callable: median and (min, max) over REPS windows of PER_REP launches, alternating."""
+    for fn in fns:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    ms = [[] for _ in fns]
+    for _ in range(REPS):
+        for k, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(PER_REP):
+                fn()
+            b.record()
+            b.synchronize()
+            ms[k].append(a.elapsed_time(b) / PER_REP)
+    return [{'median_ms': round(float(np.median(m)), 4), 'min_ms': round(min(m), 4), 'max_ms': round(max(m), 4)} for m in ms]
+
+
+def mel_for(fs, out, n_out_total):
+    """The log-mel launch over the 640 windows of `out` (deferred finish, as generate runs it)."""
+    from neural_audio_fp_amd.model.fp.melspec.melspectrogram import Melspec_layer
+    if fs != 8000:
+        os.environ['NAFP_MELSPEC_ANY'] = '1'
+    layer = Melspec_layer(input_shape=(1, fs), fs=fs, f_max=fs / 2.0)
+    off = torch.arange(SEGMENTS, dtype=torch.int64, device='cuda') * (fs // 2)
+    valid = torch.full((SEGMENTS,), fs, dtype=torch.int32, device='cuda')
+    assert int(off[-1]) + fs <= n_out_total
+    return lambda: layer.forward_windows(out, off, valid, group_size=SEGMENTS, defer=True)
+
+
+def main():
+    from neural_audio_fp_amd.model.utils import ingest as ig
+    from neural_audio_fp_amd.model.utils import resample as rs
+    from neural_audio_fp_amd import _lib
+    res = {'device': torch.cuda.get_device_name(0), 'segments': SEGMENTS, 'reps': REPS, 'launches_per_rep': PER_REP}
+    rng = np.random.default_rng(7)
+
+    # 1. 16-bit stereo 44.1 kHz: both kernels on the same samples
+    p_new, raw_bytes, n_out = pieces_for(ig, 44100, 8000, 4, 1, (2, _lib.INGEST_FORMATS['s16'][0], 0))
+    p_old, _, _ = pieces_for(rs, 44100, 8000, 4, 2, (2,))
+    raw = torch.from_numpy(rng.integers(-32768, 32768, size=raw_bytes // 2).astype(np.int16)).cuda()
+    out_new = torch.zeros((n_out,), dtype=torch.int16, device='cuda')
+    out_old = torch.zeros((n_out,), dtype=torch.int16, device='cuda')
+    d_new = torch.from_numpy(p_new.view(np.uint8).reshape(-1)).cuda()
+    d_old = torch.from_numpy(p_old.view(np.uint8).reshape(-1)).cuda()
+    plan_new, plan_old = ig.plan_for(44100, 8000), rs.plan_for(44100, 8000)
+    ig.check_pieces(44100, 8000, p_new, raw.numel() * 2, n_out)
+    rs.check_pieces(44100, 8000, p_old, raw.numel(), n_out)
+    lib, st = _lib.load(), _lib.current_stream()
+    # the library entry points themselves: the timed window holds no host-side piece checks
+    f_new = lambda: _lib.check(lib.nafp_ingest_i16(plan_new.handle, _lib.ptr(raw), raw.numel() * 2, _lib.ptr(d_new), len(p_new),
+                                                   _lib.ptr(out_new), n_out, st), 'ingest_i16')
+    f_old = lambda: _lib.check(lib.nafp_resample_i16(plan_old.handle, _lib.ptr(raw), raw.numel(), _lib.ptr(d_old), len(p_old),
+                                                     _lib.ptr(out_old), n_out, st), 'resample_i16')
+    t_new, t_old = timed([f_new, f_old])
+    res['s16x2_44100_to_8000'] = {'ingest': t_new, 'resample': t_old, 'ratio': round(t_new['median_ms'] / t_old['median_ms'], 3),
+                                  'identical': bool(torch.equal(out_new, out_old)), 'pieces': len(p_new), 'outputs': int(n_out),
+                                  'taps_per_output': plan_new.T}
+
+    # 2. 24-bit stereo 48 kHz -> 8 kHz and 16-bit mono 11.025 kHz -> 16 kHz, next to the log-mel of the same launch
+    for name, fs_in, fs_out, fmt, ch in (('s24x2_48000_to_8000', 48000, 8000, 's24', 2), ('s16x1_11025_to_16000', 11025, 16000, 's16', 1)):
+        code, width = _lib.INGEST_FORMATS[fmt]
+        pcs, raw_bytes, n_out = pieces_for(ig, fs_in, fs_out, ch * width, 1, (ch, code, 0))
+        raw = torch.from_numpy(rng.integers(0, 256, size=raw_bytes).astype(np.uint8)).cuda()
+        out = torch.zeros((n_out,), dtype=torch.int16, device='cuda')
+        d_p = torch.from_numpy(pcs.view(np.uint8).reshape(-1)).cuda()
+        plan = ig.plan_for(fs_in, fs_out)
+        ig.check_pieces(fs_in, fs_out, pcs, raw_bytes, n_out)
+        fns = [lambda: _lib.check(lib.nafp_ingest_i16(plan.handle, _lib.ptr(raw), raw_bytes, _lib.ptr(d_p), len(pcs), _lib.ptr(out),
+                                                      n_out, st), 'ingest_i16')]
+        entry = {'pieces': len(pcs), 'outputs': int(n_out), 'taps_per_output': plan.T, 'raw_bytes': int(raw_bytes)}
+        try:
+            mel = mel_for(fs_out, out, n_out)
+            mel()
+            fns.append(mel)
+        except Exception as e:                                    # the ingest figure stands without its neighbour
+            entry['log_mel_error'] = repr(e)
+        t = timed(fns)
+        entry['ingest'] = t[0]
+        if len(t) > 1:
+            entry['log_mel'] = t[1]
+        res[name] = entry
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    if not torch.cuda.is_available():
+        sys.exit('ingest_bench: no GPU; a CPU run measures nothing')
+    main()

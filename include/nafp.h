@@ -570,7 +570,8 @@ int nafp_specaug_range(const float* feat, int64_t n, float* scale_offset_out, vo
 /* One parameter tensor with its gradient and moment slots (all device pointers, float32).
  * var_len = length of ONE keras variable inside the tensor: numel for the conv / LN tensors;
  * the stacked divide-and-encode tensors hold 128 variables each (var_len = numel / 128), and
- * LAMB takes its trust ratio per variable, as the reference does over its 576 variables. */
+ * LAMB takes its trust ratio per variable, as the reference does over its 576 variables.
+ * nafp_adam_step and nafp_lamb_step check the WHOLE table before their first launch: a refused step leaves every tensor untouched. */
 typedef struct {
     float* param; const float* grad; float* m; float* v;
     int64_t numel; int64_t var_len;

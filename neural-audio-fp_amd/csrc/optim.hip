@@ -182,13 +182,30 @@ __global__ __launch_bounds__(256) void lamb_apply_kernel(const OptTable t, float
     }
 }
 
+static bool tensor_ok(const nafp_opt_tensor& t) {
+    return t.param && t.grad && t.m && t.v && t.numel > 0 && t.var_len > 0 && t.numel % t.var_len == 0;
+}
+
+// The WHOLE table is checked before the first launch: the launches take OPT_MAX_T tensors each, and a step that is refused
+// because of tensor 48 or later must not have updated tensors 0..47 already.
+static int check_tensors(const nafp_opt_tensor* ts, int n) {
+    for (int first = 0; first < n; first += OPT_MAX_T) {
+        long long blk = 0;
+        for (int i = first; i < n && i < first + OPT_MAX_T; ++i) {
+            if (!tensor_ok(ts[i])) return NAFP_ERR_INVALID_ARG;
+            blk += (ts[i].numel + OPT_BLK - 1) / OPT_BLK;
+            if (blk > 0x7fffffffll) return NAFP_ERR_UNSUPPORTED;
+        }
+    }
+    return NAFP_OK;
+}
+
 static int fill_table(OptTable& tb, const nafp_opt_tensor* ts, int first, int n, long long& norm_cursor) {
     tb.n = n;
     tb.blk0[0] = 0;
     for (int i = 0; i < n; ++i) {
         const nafp_opt_tensor& t = ts[first + i];
-        if (!t.param || !t.grad || !t.m || !t.v || t.numel <= 0 || t.var_len <= 0 || t.numel % t.var_len != 0)
-            return NAFP_ERR_INVALID_ARG;
+        if (!tensor_ok(t)) return NAFP_ERR_INVALID_ARG;
         tb.p[i] = t.param; tb.g[i] = t.grad; tb.m[i] = t.m; tb.v[i] = t.v;
         tb.numel[i] = t.numel; tb.var_len[i] = t.var_len; tb.norm_off[i] = norm_cursor;
         norm_cursor += t.numel / t.var_len;
@@ -232,6 +249,7 @@ extern "C" float nafp_cosine_decay_restarts_lr_host(float lr0, int64_t step, int
 extern "C" int nafp_adam_step(const nafp_opt_tensor* tensors_host, int n, float lr, float beta1, float beta2,
                               float eps, int64_t step, void* stream) {
     if (!tensors_host || n <= 0 || step < 1) return NAFP_ERR_INVALID_ARG;
+    if (const int rc = check_tensors(tensors_host, n)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
     const float lr_t = (float)((double)lr * sqrt(bc2) / bc1);
@@ -264,6 +282,7 @@ extern "C" int nafp_lamb_step(const nafp_opt_tensor* tensors_host, int n, float 
     const int64_t need = nafp_lamb_workspace_bytes(tensors_host, n);
     if (need < 0) return NAFP_ERR_INVALID_ARG;
     if (workspace_bytes < need) return NAFP_ERR_WORKSPACE;
+    if (const int rc = check_tensors(tensors_host, n)) return rc;
     hipStream_t st = (hipStream_t)stream;
     double* norms = (double*)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
     NAFP_HIP_CHECK(hipMemsetAsync(norms, 0, (size_t)(need - 256), st));

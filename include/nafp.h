@@ -276,6 +276,75 @@ int nafp_ingest_i16(nafp_ingest* plan, const uint8_t* raw_bytes, int64_t raw_siz
                     int64_t n_pieces, int16_t* out, int64_t out_samples, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Block codecs in RIFF/WAVE: G.711 A-law and mu-law, IMA ADPCM and MS ADPCM at 4 bits (csrc/codec.hip, the arithmetic in
+ * csrc/codec_decode.h; numpy restatement tests/_codec_ref.py).  A PRE-PASS of nafp_ingest_*, which is
+ * unchanged: whole blocks are decoded to interleaved 16-bit PCM in a device arena, which nafp_ingest_i16 then reads as
+ * NAFP_INGEST_S16.  A "block" is block_align bytes and yields spb (samples per block) frames of C = channels interleaved int16.
+ * ALL ARITHMETIC IS int32 AND EXACT: a decoded sample is a pure function of (its block's bytes, its place in the block),
+ * whatever shares its piece, workgroup or launch.  For all codecs block_align <= 4096.
+ *
+ * G.711 -- C = 1..8, block_align = C, spb = 1; per byte:
+ *   mu-law: u = ~byte & 0xff;  t = (((u & 15) << 3) + 0x84) << ((u & 0x70) >> 4);  x = (u & 0x80) ? 0x84 - t : t - 0x84
+ *   A-law:  a = byte ^ 0x55;  t = (a & 15) << 4;  seg = (a & 0x70) >> 4;
+ *           seg 0: t += 8;  seg 1: t += 0x108;  otherwise t = (t + 0x108) << (seg - 1);  x = (a & 0x80) ? t : -t
+ *   (|x| <= 32124 for mu-law, <= 32256 for A-law.)
+ * IMA ADPCM, 4 bits -- C = 1 or 2; block_align - 4 C = 4 C G with G >= 1, spb = 8 G + 1.
+ *   Layout: per channel a 4-byte header (int16 predictor, uint8 step index, one ignored byte); the predictor is frame 0.  Then
+ *   G groups; group g holds, for each channel in order, 4 bytes = the 8 nibbles of frames 1 + 8 g .. 8 + 8 g, bytes ascending,
+ *   LOW nibble first.  The header's step index is clamped to 0..88.  Per nibble n:
+ *     s = STEP[idx];  d = s >> 3;  d += s >> 2 if n & 1;  d += s >> 1 if n & 2;  d += s if n & 4;
+ *     pred = clamp16(n & 8 ? pred - d : pred + d);  idx = clamp(idx + IDX[n], 0, 88)
+ *   STEP: the standard 89 entries (7, 8, 9, ... 29794, 32767); IDX = {-1, -1, -1, -1, 2, 4, 6, 8} for n & 7.
+ * MS ADPCM, 4 bits -- C = 1 or 2; block_align > 7 C, spb = 2 + 2 (block_align - 7 C) / C.
+ *   Layout: C bytes bPredictor, C x int16 iDelta, C x int16 iSamp1, C x int16 iSamp2; frame 0 is iSamp2, frame 1 is iSamp1.
+ *   Body nibbles HIGH nibble first, round-robin over the channels: nibble k is frame 2 + k / C, channel k % C.
+ *   Coefficients (c1, c2): (256,0) (512,-256) (0,0) (192,64) (240,0) (460,-208) (392,-232); a bPredictor above 6 uses pair 6.
+ *   Per nibble n, s = n - 16 if n >= 8 else n:
+ *     pred = (samp1 c1 + samp2 c2) / 256, C division TRUNCATING TOWARD ZERO (the Microsoft text; a shift differs by one LSB on
+ *     negative sums);  x = clamp16(pred + s delta);  samp2 = samp1;  samp1 = x;
+ *     delta = clamp((ADAPT[n] delta) >> 8, 16, 2796202), arithmetic shift (2796202 = INT_MAX / 768: every product fits int32);
+ *   ADAPT = {230,230,230,230,307,409,512,614,768,614,512,409,307,230,230,230}.  The header's iDelta, sign-extended, is used as
+ *   it stands for the first nibble.
+ * Status: a codec, channel count or block_align outside the lists NAFP_ERR_UNSUPPORTED, null pointers / negative sizes / an
+ * inconsistent piece NAFP_ERR_INVALID_ARG, all before any GPU call.
+ * ---------------------------------------------------------------------- */
+#define NAFP_CODEC_ALAW 1
+#define NAFP_CODEC_ULAW 2
+#define NAFP_CODEC_IMA4 3
+#define NAFP_CODEC_MS4 4
+
+/* A run of whole blocks of one file.  40 bytes. */
+typedef struct nafp_codec_piece {
+    int64_t raw_off;      /* byte index in the raw arena of the first block (any alignment) */
+    int64_t n_blocks;     /* whole blocks */
+    int64_t out_off;      /* int16 index in the output arena of frame 0, channel 0 of the first block (any parity) */
+    int32_t codec;        /* NAFP_CODEC_* */
+    int32_t channels;
+    int32_t block_align;
+    int32_t spb;          /* nafp_codec_samples_per_block(codec, channels, block_align) */
+} nafp_codec_piece;
+
+/* Host only: frames per block, or -1 for anything outside the lists above. */
+int nafp_codec_samples_per_block(int codec, int channels, int block_align);
+/* Host only: how many blocks one workgroup of the kernel takes at a time (G.711: the frames one workgroup step covers), -1 as
+ * above.  The bytes written do not depend on it; tests cut pieces around it. */
+int nafp_codec_blocks_per_group(int codec, int channels, int block_align);
+/* Host only: n_blocks blocks at `bytes` -> n_blocks * spb * channels int16 -- the function the kernel decodes with, compiled
+ * for the host. */
+int nafp_codec_decode_host(int codec, int channels, int block_align, const void* bytes, int64_t n_blocks, int16_t* out);
+/* Host only: the checks the kernel makes per piece. */
+int nafp_codec_check_pieces_host(const nafp_codec_piece* pieces_host, int64_t n_pieces, int64_t raw_size, int64_t out_samples);
+/* raw_bytes (raw_size bytes) -> out (out_samples int16) for the n_pieces pieces of pieces_dev, all device pointers.  Every
+ * index derived from a piece is checked on the device against raw_size / out_samples.  The output range of a piece is the one
+ * it states: n_blocks * spb * channels int16 at out_off.  A piece whose range is not a range of the arena (or whose n_blocks,
+ * spb or channels cannot state one: negative, spb > 8185, channels outside 1..8) writes nothing; any other inconsistent piece
+ * (codec, channels, block_align or spb outside the lists or not matching, raw range outside the arena) is skipped and its range
+ * zeroed.  No byte outside the two arenas is read or written whatever a piece says; int16 outside the pieces' output ranges
+ * is not touched. */
+int nafp_codec_decode_i16(const uint8_t* raw_bytes, int64_t raw_size, const nafp_codec_piece* pieces_dev, int64_t n_pieces,
+                          int16_t* out, int64_t out_samples, void* stream);
+
+/* ------------------------------------------------------------------------
  * Encoder: FingerPrinter (model/fp/nnfp.py:159-231)
  * ---------------------------------------------------------------------- */
 

@@ -57,6 +57,11 @@ PROTOTYPES = {
     'nafp_ingest_create': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int]),
     'nafp_ingest_destroy': (c_int, [c_void_p]),
     'nafp_ingest_i16': (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p]),
+    'nafp_codec_samples_per_block': (c_int, [c_int, c_int, c_int]),
+    'nafp_codec_blocks_per_group': (c_int, [c_int, c_int, c_int]),
+    'nafp_codec_decode_host': (c_int, [c_int, c_int, c_int, c_void_p, c_i64, c_void_p]),
+    'nafp_codec_check_pieces_host': (c_int, [c_void_p, c_i64, c_i64, c_i64]),
+    'nafp_codec_decode_i16': (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p]),
     'nafp_encoder_create': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int]),
     'nafp_encoder_create_ex': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int]),
     'nafp_encoder_norm': (c_int, [c_void_p]),
@@ -188,6 +193,12 @@ INGEST_PIECE_DTYPE = [('raw_off', '<i8'), ('frame0', '<i8'), ('n_frames', '<i8')
                       ('out_off', '<i8'), ('n_out', '<i4'), ('channels', '<i4'), ('format', '<i4'), ('reserved', '<i4')]
 # NAFP_INGEST_* format codes (include/nafp.h): name -> (code, bytes per sample)
 INGEST_FORMATS = {'u8': (1, 1), 's16': (2, 2), 's24': (3, 3), 's32': (4, 4), 'f32': (5, 4), 'f64': (6, 8)}
+
+# nafp_codec_piece (include/nafp.h) as a numpy structured dtype: 40 bytes per piece; raw_off counts BYTES, out_off int16
+CODEC_PIECE_DTYPE = [('raw_off', '<i8'), ('n_blocks', '<i8'), ('out_off', '<i8'), ('codec', '<i4'), ('channels', '<i4'),
+                     ('block_align', '<i4'), ('spb', '<i4')]
+# NAFP_CODEC_* codes (include/nafp.h): the `format` name riff_scan_ex gives such a file -> code
+CODECS = {'alaw': 1, 'ulaw': 2, 'ima4': 3, 'ms4': 4}
 
 
 class NafpError(RuntimeError):

@@ -439,6 +439,7 @@ def generate_fingerprint(cfg, checkpoint_name, checkpoint_index, source_root_dir
         print(f"=== Generating fingerprint from \x1b[1;32m'{key}'\x1b[0m bsz={bsz}, {n_items} items, d={dim} ===")
         files = getattr(ds[key], 'ev', ds[key])    # a synthesising sequence ('unseen_syn'): the store of its event files
         if getattr(files, 'ingest', False):        # NAFP_INGEST_ANY=1: any PCM / float format, channel count and rate
+            # (NAFP_INGEST_CODECS=1 includes it: A-law, mu-law and ADPCM files are counted and named here too, e.g. '8000x1xalaw')
             from .utils.ingest import rates_summary
             source_rates[key] = rates_summary(files)
             print(f"'{key}': {source_rates[key]['resampled']} of {source_rates[key]['files']} files are decoded, mixed down and "

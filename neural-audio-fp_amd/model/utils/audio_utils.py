@@ -64,7 +64,47 @@ _PCM_WIDTHS = {1: 'u8', 2: 's16', 3: 's24', 4: 's32'}
 _FLOAT_WIDTHS = {4: 'f32', 8: 'f64'}
 
 
-def riff_scan_ex(filename, fs=None):
+_CODEC_TAGS = {0x0006: ('alaw', 'A-law'), 0x0007: ('ulaw', 'mu-law'), 0x0011: ('ima4', 'IMA ADPCM'), 0x0002: ('ms4', 'MS ADPCM')}
+_MS_COEFS = (256, 0, 512, -256, 0, 0, 192, 64, 240, 0, 460, -208, 392, -232)
+
+
+def _codec_header(filename, fmt, tag, ch, align, bits):
+    """The checks of a codec file's fmt chunk (riff_scan_ex with codecs=True): (format name, samples per block), or ValueError by
+    name.  `tag` is the format tag, or for an extensible header the tag its sub-format GUID carries (6 or 7 only)."""
+    from . import codecs as cd
+    name, title = _CODEC_TAGS[tag]
+    if name in ('alaw', 'ulaw'):
+        if bits != 8:
+            raise ValueError(f'{filename}: {bits}-bit {title} samples; G.711 is taken at 8 bits')
+        if align != ch:
+            raise ValueError(f'{filename}: block_align {align} != {ch} channels of 1-byte {title} samples')
+        return name, 1
+    if ch > 2:
+        raise ValueError(f'{filename}: {title} with {ch} channels; 1 or 2 are taken')
+    if bits != 4:
+        raise ValueError(f'{filename}: {bits}-bit {title}; 4 bits are taken')
+    if align > cd.MAX_BLOCK_ALIGN:
+        raise ValueError(f'{filename}: {title} block_align {align}; up to {cd.MAX_BLOCK_ALIGN} is taken')
+    spb = cd.samples_per_block(name, ch, align)
+    if spb < 0:
+        raise ValueError(f'{filename}: block_align {align} is not a block of {ch}-channel {title}')
+    if len(fmt) < 20:
+        raise ValueError(f'{filename}: {title} fmt chunk of {len(fmt)} bytes holds no wSamplesPerBlock')
+    w_spb, = struct.unpack('<H', fmt[18:20])
+    if w_spb != spb:
+        raise ValueError(f'{filename}: wSamplesPerBlock {w_spb} != {spb}, which {title} blocks of {align} bytes hold')
+    if name == 'ms4':
+        if len(fmt) < 22:
+            raise ValueError(f'{filename}: {title} fmt chunk of {len(fmt)} bytes holds no wNumCoef')
+        n_coef, = struct.unpack('<H', fmt[20:22])
+        if n_coef != 7:
+            raise ValueError(f'{filename}: {title} wNumCoef {n_coef}; the 7 standard coefficient pairs are taken')
+        if len(fmt) < 50 or struct.unpack('<14h', fmt[22:50]) != _MS_COEFS:
+            raise ValueError(f'{filename}: {title} coefficient table differs from the standard one')
+    return name, spb
+
+
+def riff_scan_ex(filename, fs=None, codecs=False):
     """Header scan of a RIFF/WAVE file for the general ingest (NAFP_INGEST_ANY=1, utils/ingest.py), WITHOUT reading the samples:
     {'rate', 'channels', 'format' ('u8' | 's16' | 's24' | 's32' | 'f32' | 'f64'), 'width' (bytes per sample in the file),
     'block_align', 'offset' (byte offset of the first sample), 'n_frames'}.
@@ -72,8 +112,16 @@ def riff_scan_ex(filename, fs=None):
     sub-format GUID is the PCM or the IEEE-float one -- there the container width is block_align / channels (samples are
     MSB-justified in it, so wValidBitsPerSample is not needed); 1 to 8 channels; block_align == channels * width.  Everything
     else raises ValueError by name, and with `fs` given so does a rate that cannot be brought to fs, in the reference's wording
-    (audio_utils.py:160-169)."""
+    (audio_utils.py:160-169).
+    codecs=True (NAFP_INGEST_CODECS=1, utils/codecs.py): tags 6 (A-law), 7 (mu-law), 0x11 (IMA ADPCM) and 2 (MS ADPCM) are taken
+    too, and an extensible header whose sub-format GUID carries 6 or 7 (extensible ADPCM stays refused).  G.711: 8 bits,
+    block_align == channels.  ADPCM: 4 bits, 1 or 2 channels, block_align <= 4096 and of the codec's form, wSamplesPerBlock
+    equal to what block_align holds; MS: wNumCoef == 7 and the standard pairs.  'format' is then 'alaw' | 'ulaw' | 'ima4' |
+    'ms4', 'width' 0, and the dict gains 'codec' (the same name; None for a PCM / float file) and 'samples_per_block' (spb; 1
+    for a PCM / float file).  n_frames: whole = (data bytes // block_align) * spb, a trailing partial block ignored; a `fact`
+    chunk whose first uint32 n satisfies 0 < n <= whole gives n_frames = n."""
     size = os.path.getsize(filename)
+    fact = None
     with open(filename, 'rb') as f:
         head = f.read(12)
         if len(head) < 12 or head[:4] != b'RIFF' or head[8:12] != b'WAVE':
@@ -88,6 +136,10 @@ def riff_scan_ex(filename, fs=None):
                 fmt = f.read(csz + (csz & 1))[:csz]
                 if len(fmt) < 16:
                     raise ValueError(f'{filename}: fmt chunk of {len(fmt)} bytes')
+            elif cid == b'fact' and codecs:
+                body = f.read(csz + (csz & 1))[:csz]
+                if len(body) >= 4:
+                    fact, = struct.unpack('<I', body[:4])
             elif cid == b'data':
                 if fmt is None:
                     raise ValueError(f'{filename}: data chunk before fmt chunk')
@@ -99,25 +151,40 @@ def riff_scan_ex(filename, fs=None):
     tag, ch, rate, _, align, bits = struct.unpack('<HHIIHH', fmt[:16])
     if ch < 1 or ch > 8:
         raise ValueError(f'{filename}: {ch} channels; 1 to 8 are taken')
+    codec = None
     if tag == 0xFFFE:
         if len(fmt) < 40:
             raise ValueError(f'{filename}: extensible fmt chunk of {len(fmt)} bytes')
         guid = fmt[24:40]
-        if guid[2:] != _GUID_TAIL or guid[:2] not in (b'\x01\x00', b'\x03\x00'):
-            raise ValueError(f'{filename}: extensible header with unknown sub-format GUID {guid.hex()}; taken: PCM, IEEE float')
+        if codecs and guid[2:] == _GUID_TAIL and guid[:2] in (b'\x06\x00', b'\x07\x00'):
+            codec = _codec_header(filename, fmt, guid[0], ch, align, bits)
+        elif guid[2:] != _GUID_TAIL or guid[:2] not in (b'\x01\x00', b'\x03\x00'):
+            raise ValueError(f'{filename}: extensible header with unknown sub-format GUID {guid.hex()}; taken: PCM, IEEE float' +
+                             (', A-law, mu-law' if codecs else ''))
         kind = guid[0]
-        if align % ch:
-            raise ValueError(f'{filename}: block_align {align} is not a multiple of {ch} channels')
-        width = align // ch
+        if codec is None:
+            if align % ch:
+                raise ValueError(f'{filename}: block_align {align} is not a multiple of {ch} channels')
+            width = align // ch
     elif tag in (1, 3):
         kind = tag
         if bits % 8:
             raise ValueError(f'{filename}: {bits}-bit samples; taken: PCM at 8 / 16 / 24 / 32 bits, IEEE float at 32 / 64')
         width = bits // 8
+    elif codecs and tag in _CODEC_TAGS:
+        codec = _codec_header(filename, fmt, tag, ch, align, bits)
     else:
         name = _WAVE_TAGS.get(tag)
         raise ValueError(f'{filename}: WAVE format tag 0x{tag:04x}' + (f' ({name})' if name else '') +
                          ' is not taken; taken: PCM (1), IEEE float (3), extensible (0xfffe) holding either')
+    if codec is not None:
+        name, spb = codec
+        if fs is not None:
+            from . import ingest as ig
+            ig.check_rate(rate, fs)
+        whole = (csz // align) * spb
+        return {'rate': rate, 'channels': ch, 'format': name, 'width': 0, 'block_align': align, 'offset': off,
+                'n_frames': fact if fact is not None and 0 < fact <= whole else whole, 'codec': name, 'samples_per_block': spb}
     name = (_PCM_WIDTHS if kind == 1 else _FLOAT_WIDTHS).get(width)
     if name is None:
         raise ValueError(f'{filename}: {8 * width}-bit {"PCM" if kind == 1 else "IEEE float"} samples; taken: PCM at 8 / 16 / 24 / 32 '
@@ -127,8 +194,11 @@ def riff_scan_ex(filename, fs=None):
     if fs is not None:
         from . import ingest as ig
         ig.check_rate(rate, fs)
-    return {'rate': rate, 'channels': ch, 'format': name, 'width': width, 'block_align': align, 'offset': off,
+    info = {'rate': rate, 'channels': ch, 'format': name, 'width': width, 'block_align': align, 'offset': off,
             'n_frames': csz // align}
+    if codecs:
+        info['codec'], info['samples_per_block'] = None, 1
+    return info
 
 
 def wav_info(filename, fs):
@@ -176,8 +246,12 @@ def _resample_on():
     return os.environ.get('NAFP_RESAMPLE', '') == '1'
 
 
+def _codecs_on():
+    return os.environ.get('NAFP_INGEST_CODECS', '') == '1'
+
+
 def _ingest_on():
-    return os.environ.get('NAFP_INGEST_ANY', '') == '1'
+    return os.environ.get('NAFP_INGEST_ANY', '') == '1' or _codecs_on()          # NAFP_INGEST_CODECS=1 includes it
 
 
 class SegmentSource:
@@ -198,20 +272,24 @@ class SegmentSource:
         # n_frames is then the length at the model rate, n_in / rate / channels describe the file itself
         # NAFP_INGEST_ANY=1 (includes the above): any PCM / float format, 1 to 8 channels, rates in either direction
         # (utils/ingest.py); `format` / `block_align` then describe the file's samples, and the raw arena of a launch holds BYTES
+        # NAFP_INGEST_CODECS=1 (includes both): A-law, mu-law, IMA and MS ADPCM too (utils/codecs.py); `spb` is then the frames per
+        # block_align bytes (1 for PCM / float), n_in the file's frame count, and a launch decodes whole blocks in a pre-pass
+        self.codecs = _codecs_on()
         self.ingest = _ingest_on()
         self.resample = _resample_on() or self.ingest
         self.rate, self.channels, self.n_in, self.resampled = [], [], [], []
-        self.format, self.block_align = [], []
+        self.format, self.block_align, self.spb = [], [], []
         for fn in self.fns:                      # ONE header scan per file (the reference re-opens per segment)
             if fn[-3:] != 'wav':
                 raise NotImplementedError(fn[-3:])
             if self.ingest:
                 from . import ingest as ig
-                info = riff_scan_ex(fn, fs)
+                info = riff_scan_ex(fn, fs, codecs=True) if self.codecs else riff_scan_ex(fn, fs)
                 rate, ch, off, nfr = info['rate'], info['channels'], info['offset'], info['n_frames']
                 native = ig.is_native(info, fs)
                 n_model = nfr if native else ig.n_out(nfr, rate, fs)
                 self.format.append(info['format']); self.block_align.append(info['block_align'])
+                self.spb.append(info.get('samples_per_block', 1))
                 self.n_frames.append(n_model); self.data_offset.append(off)
                 self.rate.append(rate); self.channels.append(ch); self.n_in.append(nfr); self.resampled.append(not native)
                 continue
@@ -368,12 +446,17 @@ class SegmentSource:
         """`_resample_chunk` for NAFP_INGEST_ANY=1: (raw arena, used, seg_offset, seg_valid, ingest.ChunkPieces).  `arena` (int16
         units, as `alloc` hands it out; `used` counts them) holds the files' BYTES: for every piece the byte range
         nafp_ingest_input_range x block_align, read as the file has it, piece starts 16-B aligned.  seg_offset / seg_valid index
-        the model-rate arena of `total` samples, unchanged.  Native files go the same way in such a launch (identity plan)."""
+        the model-rate arena of `total` samples, unchanged.  Native files go the same way in such a launch (identity plan).
+        A codec file (NAFP_INGEST_CODECS=1) uploads the WHOLE BLOCKS that cover its frame range; the launch's pre-pass
+        (codecs.PrePass) decodes them into an int16 scratch tensor and the file's ingest piece indexes that tensor as 16-bit PCM."""
         from . import ingest as ig
+        from . import codecs as cd
         seg_len, hop_len = self.seg_len, self.hop_len
         raw_bytes, spans = 0, []
         for f, a, b, s0, s1, base, o in pieces:
             first, last = ig.input_range(s0, s1, self.n_in[f], self.rate[f], self.fs) if s1 > s0 else (0, 0)
+            if self.format[f] in cd.CODECS:          # frames -> the blocks that hold them
+                first, last = cd.block_range(first, last, self.spb[f])
             spans.append((first, last, raw_bytes))
             raw_bytes += ((last - first) * self.block_align[f] + 15) // 16 * 16
         used = raw_bytes // 2
@@ -381,7 +464,7 @@ class SegmentSource:
         raw = arena.view(np.uint8)
         seg_offset = np.empty(n, np.int64)
         seg_valid = np.empty(n, np.int32)
-        by_rate = {}
+        by_rate, by_rate_decoded, codec_rows, scratch = {}, {}, [], 0
         for (f, a, b, s0, s1, base, o), (first, last, raw_base) in zip(pieces, spans):
             align = self.block_align[f]
             if last > first:
@@ -389,10 +472,22 @@ class SegmentSource:
                     fh.seek(self.data_offset[f] + align * first)
                     if fh.readinto(memoryview(raw[raw_base:raw_base + (last - first) * align])) != align * (last - first):
                         raise IOError(f'{self.fns[f]}: short read')
-            by_rate.setdefault(self.rate[f], []).append((raw_base, first, last - first, self.n_in[f], s0, base, s1 - s0,
-                                                         self.channels[f], ig.FORMATS[self.format[f]][0], 0))
+            if self.format[f] in cd.CODECS:
+                spb, ch = self.spb[f], self.channels[f]
+                codec_rows.append((raw_base, last - first, scratch, cd.CODECS[self.format[f]], ch, align, spb))
+                by_rate_decoded.setdefault(self.rate[f], []).append(
+                    (2 * scratch, first * spb, min((last - first) * spb, self.n_in[f] - first * spb), self.n_in[f], s0, base, s1 - s0,
+                     ch, ig.FORMATS['s16'][0], 0))
+                scratch += ((last - first) * spb * ch + 7) // 8 * 8
+            else:
+                by_rate.setdefault(self.rate[f], []).append((raw_base, first, last - first, self.n_in[f], s0, base, s1 - s0,
+                                                             self.channels[f], ig.FORMATS[self.format[f]][0], 0))
             k = np.arange(a, b, dtype=np.int64)
             seg_offset[o:o + (b - a)] = base + (k - a) * hop_len
             seg_valid[o:o + (b - a)] = np.clip(self.n_frames[f] - k * hop_len, 0, seg_len)
         by_rate = {rate: np.array(rows, dtype=ig.PIECE_DTYPE) for rate, rows in by_rate.items()}
-        return arena, used, seg_offset, seg_valid, ig.ChunkPieces(self.fs, by_rate, total)
+        if not codec_rows:
+            return arena, used, seg_offset, seg_valid, ig.ChunkPieces(self.fs, by_rate, total)
+        by_rate_decoded = {rate: np.array(rows, dtype=ig.PIECE_DTYPE) for rate, rows in by_rate_decoded.items()}
+        prepass = cd.PrePass(np.array(codec_rows, dtype=cd.PIECE_DTYPE), scratch)
+        return arena, used, seg_offset, seg_valid, ig.ChunkPieces(self.fs, by_rate, total, prepass, by_rate_decoded)

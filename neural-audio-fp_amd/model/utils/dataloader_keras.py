@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from ... import _lib
-from .audio_utils import n_segments, riff_scan, riff_scan_ex, _resample_on, _ingest_on
+from .audio_utils import n_segments, riff_scan, riff_scan_ex, _resample_on, _ingest_on, _codecs_on
 
 MAX_IR_LENGTH = 600          # dataloader_keras.py:8
 
@@ -62,21 +62,24 @@ class PcmStore:
         self.fns, self.fs = list(fns), fs
         self.n_frames, self.data_offset, self.start = [], [], []
         # NAFP_INGEST_ANY=1 (includes NAFP_RESAMPLE=1): any PCM / float format, 1 to 8 channels, rates in either direction
+        # NAFP_INGEST_CODECS=1 (includes both): A-law, mu-law, IMA and MS ADPCM too; `spb` is the frames per block_align bytes
+        self.codecs = _codecs_on()
         self.ingest = _ingest_on()
         self.resample = _resample_on() or self.ingest
         self.rate, self.channels, self.n_in, self.resampled = [], [], [], []
-        self.format, self.block_align = [], []
+        self.format, self.block_align, self.spb = [], [], []
         pos = int(base)
         for fn in self.fns:
             if fn[-3:] != 'wav':
                 raise NotImplementedError(fn[-3:])
             if self.ingest:
                 from . import ingest as ig
-                info = riff_scan_ex(fn, fs)
+                info = riff_scan_ex(fn, fs, codecs=True) if self.codecs else riff_scan_ex(fn, fs)
                 rate, ch, off, nfr = info['rate'], info['channels'], info['offset'], info['n_frames']
                 native = ig.is_native(info, fs)
                 n_model = nfr if native else ig.n_out(nfr, rate, fs)
                 self.format.append(info['format']); self.block_align.append(info['block_align'])
+                self.spb.append(info.get('samples_per_block', 1))
                 self.n_frames.append(n_model); self.data_offset.append(off); self.start.append(pos)
                 self.rate.append(rate); self.channels.append(ch); self.n_in.append(nfr); self.resampled.append(not native)
                 pos += (n_model + 7) // 8 * 8
@@ -196,13 +199,17 @@ class PcmArena:
         """`_resample_file` for NAFP_INGEST_ANY=1: the file's BYTES go through the staging buffer in runs of outputs (each run
         uploads the byte range nafp_ingest_input_range x block_align) and one nafp_ingest_piece per run."""
         from . import ingest as ig
+        from . import codecs as cd
         plan = ig.plan_for(s.rate[f], s.fs, d.device)
         align, n_in, n_total, start = int(s.block_align[f]), int(s.n_in[f]), int(s.n_frames[f]), int(s.start[f])
-        fmt = ig.FORMATS[s.format[f]][0]
+        codec = cd.CODECS.get(s.format[f])          # a codec file: whole blocks are uploaded and decoded into a scratch tensor first
+        spb = int(s.spb[f]) if codec else 1
+        fmt = ig.FORMATS['s16' if codec else s.format[f]][0]
         stage_bytes = stage.numpy().view(np.uint8)
-        # outputs per run: their input span (n M / L frames + the filter's two half-widths) fits the staging buffer
+        # outputs per run: their input span (n M / L frames + the filter's two half-widths) fits the staging buffer (a codec
+        # file's span is rounded out to whole blocks: two more)
         margin = 2 * (plan.half // plan.L + 2)
-        room = len(stage_bytes) // align - margin
+        room = (len(stage_bytes) // align - (2 if codec else 0)) * spb - margin
         if room * plan.L < plan.M:
             raise NotImplementedError(f'{s.fns[f]}: staging buffer too small to convert from {s.rate[f]} Hz')
         step = max(1, min(room * plan.L // plan.M, (1 << 31) - 1))
@@ -210,13 +217,21 @@ class PcmArena:
             for n0 in range(0, n_total, step):
                 n1 = min(n_total, n0 + step)
                 first, last = ig.input_range(n0, n1, n_in, s.rate[f], s.fs)
+                if codec:
+                    first, last = cd.block_range(first, last, spb)
                 k = (last - first) * align
                 if k:
                     fh.seek(s.data_offset[f] + align * first)
                     if fh.readinto(memoryview(stage_bytes[:k])) != k:
                         raise IOError(f'{s.fns[f]}: short read')
                 raw = stage[:max((k + 1) // 2, 1)].to(d.device, non_blocking=False).view(torch.uint8)
-                piece = np.array([(0, first, last - first, n_in, n0, start + n0, n1 - n0, s.channels[f], fmt, 0)], dtype=ig.PIECE_DTYPE)
+                n_frames = last - first
+                if codec:
+                    ch = s.channels[f]
+                    pcm = torch.empty((max(n_frames * spb * ch, 1),), dtype=torch.int16, device=d.device)
+                    cd.decode(raw, np.array([(0, n_frames, 0, codec, ch, align, spb)], dtype=cd.PIECE_DTYPE), pcm)
+                    raw, first, n_frames = pcm.view(torch.uint8), first * spb, min(n_frames * spb, n_in - first * spb)
+                piece = np.array([(0, first, n_frames, n_in, n0, start + n0, n1 - n0, s.channels[f], fmt, 0)], dtype=ig.PIECE_DTYPE)
                 plan.run(raw, piece, d)
 
 

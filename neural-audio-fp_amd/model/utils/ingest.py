@@ -18,7 +18,8 @@ FORMATS = _lib.INGEST_FORMATS                      # name -> (NAFP_INGEST_* code
 
 
 def enabled():
-    return os.environ.get('NAFP_INGEST_ANY', '') == '1'
+    # NAFP_INGEST_CODECS=1 (utils/codecs.py) includes this switch
+    return os.environ.get('NAFP_INGEST_ANY', '') == '1' or os.environ.get('NAFP_INGEST_CODECS', '') == '1'
 
 
 def geometry(fs_in, fs_out):
@@ -56,8 +57,8 @@ def check_rate(rate, fs):
 
 
 def is_native(info, fs):
-    """A file the loaders read straight into the int16 arena: 16-bit PCM mono at the model rate."""
-    return info['rate'] == fs and info['channels'] == 1 and info['format'] == 's16'
+    """A file the loaders read straight into the int16 arena: 16-bit PCM mono at the model rate (never a codec file)."""
+    return info['rate'] == fs and info['channels'] == 1 and info['format'] == 's16' and not info.get('codec')
 
 
 def check_pieces(fs_in, fs_out, pieces, raw_size, out_samples):
@@ -118,10 +119,14 @@ def plan_for(fs_in, fs_out, device=None):
 
 class ChunkPieces:
     """The ingest work of one launch: raw arena (the files' bytes) -> `out_total` int16 at the model rate; `by_rate` maps fs_in
-    to the host piece array of that rate (native files ride along through the identity plan)."""
+    to the host piece array of that rate (native files ride along through the identity plan).  With NAFP_INGEST_CODECS=1 a
+    launch may hold codec files: `prepass` (utils/codecs.PrePass) then decodes their blocks from the raw arena into an int16
+    scratch tensor first, on the same stream, and `by_rate_decoded` holds the pieces (format s16) that index that tensor's
+    bytes."""
 
-    def __init__(self, fs_out, by_rate, out_total):
+    def __init__(self, fs_out, by_rate, out_total, prepass=None, by_rate_decoded=None):
         self.fs_out, self.by_rate, self.out_total = fs_out, by_rate, int(out_total)
+        self.prepass, self.by_rate_decoded = prepass, by_rate_decoded or {}
 
     def run(self, raw_dev):
         """raw_dev: the uploaded arena, uint8 or an int16 tensor over the same bytes (the loaders' pinned buffers are int16)."""
@@ -130,6 +135,10 @@ class ChunkPieces:
         out = torch.empty((max(self.out_total, 1),), dtype=torch.int16, device=raw.device)
         for fs_in, pieces in self.by_rate.items():
             plan_for(fs_in, self.fs_out, raw.device).run(raw, pieces, out)
+        if self.prepass is not None:
+            pcm = self.prepass.run(raw).view(torch.uint8)
+            for fs_in, pieces in self.by_rate_decoded.items():
+                plan_for(fs_in, self.fs_out, raw.device).run(pcm, pieces, out)
         return out
 
 

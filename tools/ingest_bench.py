@@ -8,6 +8,10 @@ alternating inside a rep so that drift hits them alike; median and range over th
      samples and pieces (outputs compared byte for byte on the way), and their ratio;
   2. 24-bit stereo at 48 kHz -> 8 kHz and 16-bit mono 11.025 kHz -> 16 kHz, next to the log-mel kernel of the same launch
      (640 windows over the ingest's output; the 16 kHz front end needs NAFP_MELSPEC_ANY=1, which this tool sets for that case).
+  3. the codec pre-pass (NAFP_INGEST_CODECS=1, csrc/codec.hip) of G.711 8 kHz mono, IMA ADPCM 22.05 kHz stereo in 1024-byte
+     blocks, MS ADPCM 44.1 kHz stereo in 2048-byte blocks and IMA ADPCM 44.1 kHz mono in 4096-byte blocks -- blocks of random
+     bytes: the decoders have no data-dependent loop -- next to two figures of the same launch: the 16-bit ingest of the samples
+     it decoded, and the log-mel kernel.
 A launch is 640 one-second segments at a hop of 0.5 s: 320.5 s of audio, cut into 30-s files as generate would (11 pieces).
 One JSON line at the end."""
 import json
@@ -39,6 +43,25 @@ def pieces_for(mod, fs_in, fs_out, frame_bytes, unit, extra):
         raw_pos += ((last - first) * frame_bytes + 15) // 16 * 16
         out_pos += (n_out + 7) // 8 * 8
     return np.array(rows, dtype=mod.PIECE_DTYPE), raw_pos, out_pos
+
+
+def codec_pieces(ig, cd, codec, fs_in, fs_out, ch, align):
+    """The launch of a codec tree as SegmentSource._ingest_chunk cuts it: per 30-s file the whole blocks that cover the frames its
+    outputs read, decoded into a scratch arena that the file's ingest piece (16-bit PCM) indexes.
+    -> (codec piece array, ingest piece array, raw bytes, scratch int16, outputs)."""
+    spb = cd.samples_per_block(codec, ch, align)
+    total_out = (SEGMENTS - 1) * (fs_out // 2) + fs_out
+    c_rows, i_rows, raw_pos, scratch, out_pos = [], [], 0, 0, 0
+    while out_pos < total_out:
+        n_in = FILE_SECONDS * fs_in
+        n_out = min(ig.n_out(n_in, fs_in, fs_out), total_out - out_pos)
+        b0, b1 = cd.block_range(*ig.input_range(0, n_out, n_in, fs_in, fs_out), spb)
+        c_rows.append((raw_pos, b1 - b0, scratch, cd.CODECS[codec], ch, align, spb))
+        i_rows.append((2 * scratch, b0 * spb, min((b1 - b0) * spb, n_in - b0 * spb), n_in, 0, out_pos, n_out, ch, ig.FORMATS['s16'][0], 0))
+        raw_pos += ((b1 - b0) * align + 15) // 16 * 16
+        scratch += ((b1 - b0) * spb * ch + 7) // 8 * 8
+        out_pos += (n_out + 7) // 8 * 8
+    return np.array(c_rows, dtype=cd.PIECE_DTYPE), np.array(i_rows, dtype=ig.PIECE_DTYPE), raw_pos, scratch, out_pos
 
 
 def timed(fns):
@@ -124,6 +147,30 @@ def main():
         if len(t) > 1:
             entry['log_mel'] = t[1]
         res[name] = entry
+
+    # 3. the codec pre-pass next to the 16-bit ingest of what it decoded and the log-mel of the same launch
+    from neural_audio_fp_amd.model.utils import codecs as cd
+    for name, codec, fs_in, ch, align in (('alaw_x1_8000', 'alaw', 8000, 1, 1), ('ima4_x2_22050_block1024', 'ima4', 22050, 2, 1024),
+                                          ('ms4_x2_44100_block2048', 'ms4', 44100, 2, 2048), ('ima4_x1_44100_block4096', 'ima4', 44100, 1, 4096)):
+        c_p, i_p, raw_bytes, scratch, n_out = codec_pieces(ig, cd, codec, fs_in, 8000, ch, align)
+        raw = torch.from_numpy(rng.integers(0, 256, size=raw_bytes).astype(np.uint8)).cuda()
+        pcm = torch.zeros((scratch,), dtype=torch.int16, device='cuda')
+        out = torch.zeros((n_out,), dtype=torch.int16, device='cuda')
+        cd.check_pieces(c_p, raw_bytes, scratch)
+        ig.check_pieces(fs_in, 8000, i_p, 2 * scratch, n_out)
+        d_c = torch.from_numpy(c_p.view(np.uint8).reshape(-1)).cuda()
+        d_i = torch.from_numpy(i_p.view(np.uint8).reshape(-1)).cuda()
+        plan = ig.plan_for(fs_in, 8000)
+        f_dec = lambda: _lib.check(lib.nafp_codec_decode_i16(_lib.ptr(raw), raw_bytes, _lib.ptr(d_c), len(c_p), _lib.ptr(pcm), scratch, st),
+                                   'codec_decode_i16')
+        f_ing = lambda: _lib.check(lib.nafp_ingest_i16(plan.handle, _lib.ptr(pcm), 2 * scratch, _lib.ptr(d_i), len(i_p), _lib.ptr(out), n_out,
+                                                       st), 'ingest_i16')
+        mel = mel_for(8000, out, n_out)
+        t = timed([f_dec, f_ing, mel])
+        res[name] = {'pieces': len(c_p), 'raw_bytes': int(raw_bytes), 'decoded_samples': int(scratch), 'outputs': int(n_out),
+                     'blocks_per_group': int(lib.nafp_codec_blocks_per_group(cd.CODECS[codec], ch, align)),
+                     'prepass': t[0], 'ingest_s16': t[1], 'log_mel': t[2],
+                     'prepass_over_ingest': round(t[0]['median_ms'] / t[1]['median_ms'], 3)}
     print(json.dumps(res))
 
 

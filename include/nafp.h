@@ -345,6 +345,96 @@ int nafp_codec_decode_i16(const uint8_t* raw_bytes, int64_t raw_size, const nafp
                           int16_t* out, int64_t out_samples, void* stream);
 
 /* ------------------------------------------------------------------------
+ * FLAC (csrc/flac.hip, the arithmetic in csrc/flac_decode.h; numpy / Python restatement tests/_flac_ref.py; DESIGN.md section
+ * 4.10.3).  A PRE-PASS of nafp_ingest_*, which is unchanged: whole frames are decoded to interleaved little-endian PCM of the
+ * file's own channel count and rate in a device BYTE arena.  A sample v of bps <= 16 bits becomes an s16 container holding
+ * v << (16 - bps), one of 17 .. 24 bits a 3-byte s24 container holding v << (24 - bps) -- the bytes of the MSB-justified PCM WAV of
+ * the same samples -- which nafp_ingest_i16 then reads as NAFP_INGEST_S16 / NAFP_INGEST_S24.
+ * Taken: native FLAC streams (an ID3v2 tag before `fLaC` is skipped), 1 .. 8 channels, 8 / 12 / 16 / 20 / 24 bits, block sizes up
+ * to 16384 in fixed- or variable-blocksize streams, constant / verbatim / fixed (order 0 .. 4) / LPC (order 1 .. 32, precision
+ * 1 .. 15, shift 0 .. 15) subframes, both Rice methods with escape partitions, wasted bits, all four channel assignments.
+ * ALL ARITHMETIC IS INTEGER AND EXACT: a prediction is sum_j coef[j] * s[i - 1 - j] in int64, shifted right arithmetically by
+ * `shift`, plus the residual, truncated to int32; fixed predictors are the same form with coefficients (1) (2,-1) (3,-3,1)
+ * (4,-6,4,-1); a side channel carries bps + 1 bits.  A decoded frame is a pure function of (its bytes, its record), whatever
+ * shares its launch.
+ * CORRUPT INPUT: every bit read is bounded by the frame's stated length, every unary run, Rice parameter, raw-bit count, LPC
+ * order (<= block size), partition order (block size divisible by 2^order, first partition >= predictor order), reserved code and
+ * write index is checked.  A frame that fails a check or its CRC-16 (polynomial 0x8005, initial 0) has its WHOLE output range
+ * zeroed and a non-zero status; a frame whose header disagrees with its record (the file's STREAMINFO) in block size, channels,
+ * depth or rate fails too; a record that states no range of the scratch arena writes nothing.  Other frames are unaffected.
+ * Status of the functions: null pointers / negative sizes / an inconsistent record NAFP_ERR_INVALID_ARG, before any GPU call.
+ * ---------------------------------------------------------------------- */
+/* per-frame status (int32): 0 = decoded */
+#define NAFP_FLAC_BAD_RECORD 1        /* raw range outside the arena, depth / rate outside the contract: range zeroed */
+#define NAFP_FLAC_BAD_HEADER 2        /* no sync, a reserved bit or code, a bad coded number or CRC-8 */
+#define NAFP_FLAC_HEADER_MISMATCH 3   /* block size, channels, depth or rate differ from the record */
+#define NAFP_FLAC_TRUNCATED 4         /* the frame's bytes end before the frame does */
+#define NAFP_FLAC_BAD_SUBFRAME 5      /* reserved type, wasted bits >= width, order > block size, precision 16, negative shift */
+#define NAFP_FLAC_BAD_RESIDUAL 6      /* reserved method, partition order, over-long unary run */
+#define NAFP_FLAC_BAD_CRC16 7
+#define NAFP_FLAC_NO_RANGE 8          /* the record states no range of the scratch arena: nothing written */
+/* nafp_flac_info.refusal: 0 = taken */
+#define NAFP_FLAC_REFUSE_OGG 1
+#define NAFP_FLAC_REFUSE_MARKER 2      /* no `fLaC` */
+#define NAFP_FLAC_REFUSE_STREAMINFO 3  /* the first metadata block is not a 34-byte STREAMINFO */
+#define NAFP_FLAC_REFUSE_DEPTH 4       /* not 8 / 12 / 16 / 20 / 24 bits */
+#define NAFP_FLAC_REFUSE_BLOCK 5       /* maximum block size above 16384 */
+
+/* 72 bytes. */
+typedef struct nafp_flac_info {
+    int64_t total_samples;    /* STREAMINFO's count of frames of audio, 0 = unknown */
+    int64_t audio_off;        /* byte offset behind the last metadata block */
+    int64_t n_indexed;        /* nafp_flac_index_host: frames in the index (may exceed the caller's cap) */
+    int64_t indexed_samples;  /* nafp_flac_index_host: sum of their block sizes */
+    int32_t rate, channels, bps, min_block, max_block, refusal;
+    uint8_t md5[16];
+} nafp_flac_info;
+
+/* One frame of the index.  32 bytes. */
+typedef struct nafp_flac_index_entry {
+    int64_t offset;        /* byte offset of the sync code in the file */
+    int64_t first_sample;  /* as coded: frame number x STREAMINFO block size, or the sample number */
+    int64_t n_bytes;       /* up to the next indexed frame, or the end of the file */
+    int32_t block_size;
+    int32_t reserved;
+} nafp_flac_index_entry;
+
+/* One frame of a launch, uploaded by the host.  40 bytes. */
+typedef struct nafp_flac_frame {
+    int64_t raw_off;       /* byte index in the raw arena of the frame's sync code (any alignment) */
+    int64_t scratch_off;   /* byte index in the scratch arena of sample 0, channel 0 (any alignment) */
+    int32_t n_bytes;       /* bytes the frame may read */
+    int32_t block_size;    /* 1 .. 16384 */
+    int32_t channels;      /* 1 .. 8, STREAMINFO's */
+    int32_t bps;           /* 8 / 12 / 16 / 20 / 24, STREAMINFO's */
+    int32_t rate;          /* STREAMINFO's */
+    int32_t reserved;
+} nafp_flac_frame;
+
+/* Host only: STREAMINFO of the stream at bytes[0, n_bytes).  NAFP_OK with info->refusal set for a stream that is not taken. */
+int nafp_flac_streaminfo_host(const void* bytes, int64_t n_bytes, nafp_flac_info* info);
+/* Host only: STREAMINFO and the frame index of a whole stream, one pass.  Candidates are found by the sync pattern and kept when
+ * their header parses (reserved bits and codes, coded number, CRC-8) and CONTINUES THE CHAIN: fixed-blocksize stream -- frame number
+ * = predecessor's + 1, first sample = number x STREAMINFO block size, only the last frame shorter; variable-blocksize stream -- coded
+ * sample number = predecessor's first sample + block size.  The chain starts at the first valid header behind the metadata, whatever
+ * its number.  A candidate that breaks continuity is dropped.  A FALSE candidate that keeps continuity by chance is not recognised
+ * here: it is caught by the frame's CRC-16 on the device and counts as a failed frame.  A last frame the file cuts short is left
+ * out.  At most `cap` entries are written to frames_out (may be NULL with cap 0); info->n_indexed counts all. */
+int nafp_flac_index_host(const void* bytes, int64_t n_bytes, nafp_flac_info* info, nafp_flac_index_entry* frames_out, int64_t cap);
+/* Host only: what nafp_flac_decode writes, from the function the kernels decode with, compiled for the host: the same scratch
+ * bytes, the same status per frame (status_out may be NULL). */
+int nafp_flac_decode_host(const void* raw, int64_t raw_size, const nafp_flac_frame* frames_host, int64_t n_frames, void* scratch,
+                          int64_t scratch_size, int32_t* status_out);
+/* Host only: the checks the kernels make per record; NAFP_ERR_INVALID_ARG for one that would not decode (status 1 or 8). */
+int nafp_flac_check_frames_host(const nafp_flac_frame* frames_host, int64_t n_frames, int64_t raw_size, int64_t scratch_size);
+/* raw (raw_size bytes) -> scratch (scratch_size bytes) for the n_frames records of frames_dev, all device pointers; status_dev:
+ * int32 per frame, may be NULL.  Every index derived from a record or from the stream is checked on the device.  No byte outside
+ * the two arenas is read or written whatever a record or a frame says; bytes outside the records' output ranges are not touched.
+ * An int32 workspace of scratch_size / 2 + 1 elements is taken from the stream-ordered allocator for the duration of the call. */
+int nafp_flac_decode(const uint8_t* raw, int64_t raw_size, const nafp_flac_frame* frames_dev, int64_t n_frames, uint8_t* scratch,
+                     int64_t scratch_size, int32_t* status_dev, void* stream);
+
+/* ------------------------------------------------------------------------
  * Encoder: FingerPrinter (model/fp/nnfp.py:159-231)
  * ---------------------------------------------------------------------- */
 

@@ -62,6 +62,11 @@ PROTOTYPES = {
     'nafp_codec_decode_host': (c_int, [c_int, c_int, c_int, c_void_p, c_i64, c_void_p]),
     'nafp_codec_check_pieces_host': (c_int, [c_void_p, c_i64, c_i64, c_i64]),
     'nafp_codec_decode_i16': (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p]),
+    'nafp_flac_streaminfo_host': (c_int, [c_void_p, c_i64, c_void_p]),
+    'nafp_flac_index_host': (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64]),
+    'nafp_flac_decode_host': (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p]),
+    'nafp_flac_check_frames_host': (c_int, [c_void_p, c_i64, c_i64, c_i64]),
+    'nafp_flac_decode': (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p]),
     'nafp_encoder_create': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int]),
     'nafp_encoder_create_ex': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int]),
     'nafp_encoder_norm': (c_int, [c_void_p]),
@@ -199,6 +204,13 @@ CODEC_PIECE_DTYPE = [('raw_off', '<i8'), ('n_blocks', '<i8'), ('out_off', '<i8')
                      ('block_align', '<i4'), ('spb', '<i4')]
 # NAFP_CODEC_* codes (include/nafp.h): the `format` name riff_scan_ex gives such a file -> code
 CODECS = {'alaw': 1, 'ulaw': 2, 'ima4': 3, 'ms4': 4}
+
+# nafp_flac_info / nafp_flac_index_entry / nafp_flac_frame (include/nafp.h) as numpy structured dtypes: 72 / 32 / 40 bytes
+FLAC_INFO_DTYPE = [('total_samples', '<i8'), ('audio_off', '<i8'), ('n_indexed', '<i8'), ('indexed_samples', '<i8'), ('rate', '<i4'),
+                   ('channels', '<i4'), ('bps', '<i4'), ('min_block', '<i4'), ('max_block', '<i4'), ('refusal', '<i4'), ('md5', 'u1', (16,))]
+FLAC_INDEX_DTYPE = [('offset', '<i8'), ('first_sample', '<i8'), ('n_bytes', '<i8'), ('block_size', '<i4'), ('reserved', '<i4')]
+FLAC_FRAME_DTYPE = [('raw_off', '<i8'), ('scratch_off', '<i8'), ('n_bytes', '<i4'), ('block_size', '<i4'), ('channels', '<i4'),
+                    ('bps', '<i4'), ('rate', '<i4'), ('reserved', '<i4')]
 
 
 class NafpError(RuntimeError):

@@ -11,8 +11,17 @@ Mirrors the parts of the reference's `Dataset` (model/dataset.py:10-323) that
 """
 import glob
 
-from .utils.audio_utils import SegmentSource
+from .utils.audio_utils import SegmentSource, _flac_on
 from .utils.dataloader_keras import genUnbalSequence
+
+
+def _audio_files(prefix):
+    """sorted(glob(prefix + '*.wav')), as the reference lists a directory; under NAFP_INGEST_FLAC=1 the names ending in `.flac` (any
+    letter case) are merged in and the whole list is sorted by path."""
+    fps = glob.glob(prefix + '*.wav', recursive=True)
+    if _flac_on():
+        fps += [p for p in glob.glob(prefix + '*', recursive=True) if p[-5:].lower() == '.flac']
+    return sorted(fps)
 
 
 class Dataset:
@@ -39,7 +48,7 @@ class Dataset:
         self.tr_use_bg_aug, self.val_use_bg_aug = aug['TR_BG_AUG'], aug['VAL_BG_AUG']
         self.tr_use_ir_aug, self.val_use_ir_aug = aug['TR_IR_AUG'], aug['VAL_IR_AUG']
         self.tr_use_speech_aug, self.val_use_speech_aug = aug['TR_SPEECH_AUG'], aug['VAL_SPEECH_AUG']
-        g = lambda root, sub: sorted(glob.glob(root + sub + '/**/*.wav', recursive=True))
+        g = lambda root, sub: _audio_files(root + sub + '/**/')
         # dataset.py:86-125: validation reuses the training split of bg / ir, speech has train / dev
         self.tr_bg_fps = g(self.bg_root_dir, 'tr') if self.tr_use_bg_aug else None
         self.val_bg_fps = g(self.bg_root_dir, 'tr') if self.val_use_bg_aug else None
@@ -62,7 +71,7 @@ class Dataset:
             _prefix = 'train-10k-30s/'
         else:
             raise NotImplementedError(self.datasel_train)
-        self.tr_source_fps = sorted(glob.glob(self.source_root_dir + _prefix + '**/*.wav', recursive=True))
+        self.tr_source_fps = _audio_files(self.source_root_dir + _prefix + '**/')
         return genUnbalSequence(
             fns_event_list=self.tr_source_fps, bsz=bsz or self.tr_batch_sz, n_anchor=n_anchor or self.tr_n_anchor,
             duration=self.dur, hop=self.hop, fs=self.fs, shuffle=True, random_offset_anchor=True,
@@ -73,8 +82,7 @@ class Dataset:
 
     def get_val_ds(self, max_song=500):
         """dataset.py:156-186."""
-        self.val_source_fps = sorted(glob.glob(self.source_root_dir + 'val-query-db-500-30s/' + '**/*.wav',
-                                               recursive=True))[:max_song]
+        self.val_source_fps = _audio_files(self.source_root_dir + 'val-query-db-500-30s/' + '**/')[:max_song]
         return genUnbalSequence(
             self.val_source_fps, self.val_batch_sz, self.val_n_anchor, self.dur, self.hop, self.fs, shuffle=False,
             random_offset_anchor=False, bg_mix_parameter=[self.val_use_bg_aug, self.val_bg_fps, self.val_snr],
@@ -83,7 +91,7 @@ class Dataset:
 
     def get_test_dummy_db_ds(self):
         """dataset.py:189-215."""
-        fps = sorted(glob.glob(self.source_root_dir + 'test-dummy-db-100k-full/' + '**/*.wav', recursive=True))
+        fps = _audio_files(self.source_root_dir + 'test-dummy-db-100k-full/' + '**/')
         sel = self.datasel_test_dummy_db
         if sel in ['10k_full', '10k_30s']:
             fps = fps[:10000]
@@ -100,13 +108,12 @@ class Dataset:
         """dataset.py:218-262 ('unseen_icassp')."""
         if self.datasel_test_query_db == 'unseen_icassp':
             root = self.source_root_dir + 'test-query-db-500-30s/'
-            self.ts_query_icassp_fps = sorted(glob.glob(root + 'query/**/*.wav', recursive=True))
-            self.ts_db_icassp_fps = sorted(glob.glob(root + 'db/**/*.wav', recursive=True))
+            self.ts_query_icassp_fps = _audio_files(root + 'query/**/')
+            self.ts_db_icassp_fps = _audio_files(root + 'db/**/')
             return self._source(self.ts_query_icassp_fps), self._source(self.ts_db_icassp_fps)
         elif self.datasel_test_query_db == 'unseen_syn':
             # dataset.py:266-304: the queries are synthesised from the DB on the fly (test split of bg / ir)
-            self.ts_query_db_unseen_fps = sorted(glob.glob(self.source_root_dir + 'val-query-db-500-30s/' + 'db/**/*.wav',
-                                                           recursive=True))
+            self.ts_query_db_unseen_fps = _audio_files(self.source_root_dir + 'val-query-db-500-30s/' + 'db/**/')
             ds_query = genUnbalSequence(
                 self.ts_query_db_unseen_fps, self.ts_batch_sz * 2, self.ts_batch_sz, self.dur, self.hop, self.fs, shuffle=False,
                 random_offset_anchor=False, bg_mix_parameter=[self.ts_use_bg_aug, self.ts_bg_fps, self.ts_snr],
@@ -118,5 +125,5 @@ class Dataset:
 
     def get_custom_db_ds(self, source_root_dir):
         """dataset.py:306-322."""
-        fps = sorted(glob.glob(source_root_dir + '/**/*.wav', recursive=True))
+        fps = _audio_files(source_root_dir + '/**/')
         return self._source(fps)

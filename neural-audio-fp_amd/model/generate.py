@@ -451,6 +451,12 @@ def generate_fingerprint(cfg, checkpoint_name, checkpoint_index, source_root_dir
                   f"{ds[key].fs} Hz mono on the device (rate x channels: files) {source_rates[key]['rates']}")
         write_fingerprints(ds[key], embed, arr, bsz, rank, world)
         arr.flush()
+        if getattr(files, 'flac', False) and key in source_rates:      # NAFP_INGEST_FLAC=1: summed on the device, read once here
+            from .utils.flac import failed_count
+            source_rates[key]['flac_files'] = len(files.flac_index)
+            source_rates[key]['flac_failed_frames'] = failed_count(files, dist)
+            print(f"'{key}': {source_rates[key]['flac_files']} FLAC files, {source_rates[key]['flac_failed_frames']} frames failed their "
+                  f"checks (header, bounds or CRC-16) and were converted as zeros")
         if dist:
             dist.barrier()
         print(f'=== Succesfully stored {arr_shape[0]} fingerprint to {output_root_dir} ===')

@@ -201,6 +201,37 @@ def riff_scan_ex(filename, fs=None, codecs=False):
     return info
 
 
+def flac_scan(filename, fs=None):
+    """STREAMINFO and frame index of a FLAC file for the general ingest (NAFP_INGEST_FLAC=1, utils/flac.py), one pass over the
+    file: what riff_scan_ex returns -- 'format' is 'flacNN' (NN = bits per sample), 'codec' 'flac', 'width' / 'block_align' /
+    'offset' 0, 'samples_per_block' 1 -- plus 'bps', 'frames' (per frame the byte offset, first sample as coded, byte length and
+    block size: a structured array) and 'index' (flac.Index over them).  n_frames is STREAMINFO's total when that is non-zero and
+    not above the indexed sum, otherwise the indexed sum.  Refused by name (ValueError): Ogg FLAC, no `fLaC` marker, a first
+    metadata block that is not a 34-byte STREAMINFO, a depth other than 8 / 12 / 16 / 20 / 24 bits, a maximum block size above
+    16384, a file without a valid frame, and with `fs` a rate that cannot be brought to fs."""
+    from . import flac as fl
+    with open(filename, 'rb') as f:
+        data = f.read()
+    info, frames = fl.scan(data)
+    refusal = int(info['refusal'])
+    if refusal == 4:
+        raise ValueError(f"{filename}: {int(info['bps'])}-bit FLAC samples; {fl.REFUSALS[4]}")
+    if refusal == 5:
+        raise ValueError(f"{filename}: FLAC maximum block size {int(info['max_block'])}; {fl.REFUSALS[5]}")
+    if refusal:
+        raise ValueError(f'{filename}: {fl.REFUSALS[refusal]}')
+    if len(frames) == 0:
+        raise ValueError(f'{filename}: no valid FLAC frame found')
+    rate, ch, bps = int(info['rate']), int(info['channels']), int(info['bps'])
+    if fs is not None:
+        from . import ingest as ig
+        ig.check_rate(rate, fs)
+    total, indexed = int(info['total_samples']), int(info['indexed_samples'])
+    return {'rate': rate, 'channels': ch, 'format': f'flac{bps}', 'width': 0, 'block_align': 0, 'offset': 0,
+            'n_frames': total if 0 < total <= indexed else indexed, 'codec': 'flac', 'samples_per_block': 1, 'bps': bps,
+            'frames': frames, 'index': fl.Index(frames, ch, bps, rate)}
+
+
 def wav_info(filename, fs):
     """Frame count of a 16-bit mono WAV; ValueError on a wrong sample rate
     (audio_utils.py:160-169)."""
@@ -246,8 +277,17 @@ def _resample_on():
     return os.environ.get('NAFP_RESAMPLE', '') == '1'
 
 
+def _flac_on():
+    return os.environ.get('NAFP_INGEST_FLAC', '') == '1'
+
+
 def _codecs_on():
-    return os.environ.get('NAFP_INGEST_CODECS', '') == '1'
+    return os.environ.get('NAFP_INGEST_CODECS', '') == '1' or _flac_on()           # NAFP_INGEST_FLAC=1 includes it
+
+
+def _taken_name(fn, flac):
+    """The loaders' name check: `wav`, and under NAFP_INGEST_FLAC=1 `.flac` in any letter case."""
+    return fn[-3:] == 'wav' or (flac and fn[-5:].lower() == '.flac')
 
 
 def _ingest_on():
@@ -274,17 +314,25 @@ class SegmentSource:
         # (utils/ingest.py); `format` / `block_align` then describe the file's samples, and the raw arena of a launch holds BYTES
         # NAFP_INGEST_CODECS=1 (includes both): A-law, mu-law, IMA and MS ADPCM too (utils/codecs.py); `spb` is then the frames per
         # block_align bytes (1 for PCM / float), n_in the file's frame count, and a launch decodes whole blocks in a pre-pass
+        # NAFP_INGEST_FLAC=1 (includes all three): `.flac` names too (utils/flac.py); `flac_index[f]` is then the file's frame index,
+        # built here by one pass over the file, and a launch decodes the whole frames that cover its samples in a pre-pass
+        self.flac = _flac_on()
+        self.flac_index = {}
         self.codecs = _codecs_on()
         self.ingest = _ingest_on()
         self.resample = _resample_on() or self.ingest
         self.rate, self.channels, self.n_in, self.resampled = [], [], [], []
         self.format, self.block_align, self.spb = [], [], []
         for fn in self.fns:                      # ONE header scan per file (the reference re-opens per segment)
-            if fn[-3:] != 'wav':
+            if not _taken_name(fn, self.flac):
                 raise NotImplementedError(fn[-3:])
             if self.ingest:
                 from . import ingest as ig
-                info = riff_scan_ex(fn, fs, codecs=True) if self.codecs else riff_scan_ex(fn, fs)
+                if fn[-3:] != 'wav':
+                    info = flac_scan(fn, fs)
+                    self.flac_index[len(self.n_frames)] = info['index']
+                else:
+                    info = riff_scan_ex(fn, fs, codecs=True) if self.codecs else riff_scan_ex(fn, fs)
                 rate, ch, off, nfr = info['rate'], info['channels'], info['offset'], info['n_frames']
                 native = ig.is_native(info, fs)
                 n_model = nfr if native else ig.n_out(nfr, rate, fs)
@@ -307,6 +355,10 @@ class SegmentSource:
                 native, n_model = True, nfr
             self.n_frames.append(n_model); self.data_offset.append(off)
             self.rate.append(rate); self.channels.append(ch); self.n_in.append(nfr); self.resampled.append(not native)
+        self.flac_failed = None
+        if self.flac_index:                      # which frames failed their checks: one byte per frame, on the device
+            from . import flac as fl
+            self.flac_failed = fl.FailedFrames([len(self.flac_index[f]) if f in self.flac_index else 0 for f in range(len(self.fns))])
         counts = [n_segments(nfr, fs, duration, hop) for nfr in self.n_frames]
         self.file_first = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         self.n_samples = int(self.file_first[-1])
@@ -448,13 +500,21 @@ class SegmentSource:
         nafp_ingest_input_range x block_align, read as the file has it, piece starts 16-B aligned.  seg_offset / seg_valid index
         the model-rate arena of `total` samples, unchanged.  Native files go the same way in such a launch (identity plan).
         A codec file (NAFP_INGEST_CODECS=1) uploads the WHOLE BLOCKS that cover its frame range; the launch's pre-pass
-        (codecs.PrePass) decodes them into an int16 scratch tensor and the file's ingest piece indexes that tensor as 16-bit PCM."""
+        (codecs.PrePass) decodes them into an int16 scratch tensor and the file's ingest piece indexes that tensor as 16-bit PCM.
+        A FLAC file (NAFP_INGEST_FLAC=1) uploads the WHOLE FRAMES that cover its sample range, one contiguous byte range of the
+        file; flac.PrePass decodes them into a byte scratch tensor of its own, indexed as 16- or 24-bit PCM."""
         from . import ingest as ig
         from . import codecs as cd
+        from . import flac as fl
         seg_len, hop_len = self.seg_len, self.hop_len
         raw_bytes, spans = 0, []
         for f, a, b, s0, s1, base, o in pieces:
             first, last = ig.input_range(s0, s1, self.n_in[f], self.rate[f], self.fs) if s1 > s0 else (0, 0)
+            if f in self.flac_index:                 # samples -> the frames that hold them; their bytes
+                first, last = fl.frame_range(self.flac_index[f], first, last)
+                spans.append((first, last, raw_bytes))
+                raw_bytes += (fl.records(self.flac_index[f], first, last, 0, 0)[1] + 15) // 16 * 16
+                continue
             if self.format[f] in cd.CODECS:          # frames -> the blocks that hold them
                 first, last = cd.block_range(first, last, self.spb[f])
             spans.append((first, last, raw_bytes))
@@ -465,14 +525,33 @@ class SegmentSource:
         seg_offset = np.empty(n, np.int64)
         seg_valid = np.empty(n, np.int32)
         by_rate, by_rate_decoded, codec_rows, scratch = {}, {}, [], 0
+        by_rate_flac, flac_rows, flac_ids, flac_scratch = {}, [], [], 0
         for (f, a, b, s0, s1, base, o), (first, last, raw_base) in zip(pieces, spans):
             align = self.block_align[f]
-            if last > first:
+            if f in self.flac_index:
+                idx = self.flac_index[f]
+                rows, n_raw, n_pcm = fl.records(idx, first, last, raw_base, flac_scratch)
+                if n_raw:
+                    with open(self.fns[f], 'rb', buffering=0) as fh:
+                        fh.seek(int(idx.offset[first]))
+                        if fh.readinto(memoryview(raw[raw_base:raw_base + n_raw])) != n_raw:
+                            raise IOError(f'{self.fns[f]}: short read')
+                    flac_rows.append(rows)
+                    flac_ids.append(self.flac_failed.base[f] + np.arange(first, last, dtype=np.int64))
+                frame0 = int(idx.start[first]) if last > first else 0
+                covered = int(idx.start[last] - idx.start[first]) if last > first else 0
+                by_rate_flac.setdefault(self.rate[f], []).append(
+                    (flac_scratch, frame0, max(0, min(covered, self.n_in[f] - frame0)), self.n_in[f], s0, base, s1 - s0, self.channels[f],
+                     ig.FORMATS['s16' if idx.bps <= 16 else 's24'][0], 0))
+                flac_scratch += (n_pcm + 15) // 16 * 16
+            elif last > first:
                 with open(self.fns[f], 'rb', buffering=0) as fh:
                     fh.seek(self.data_offset[f] + align * first)
                     if fh.readinto(memoryview(raw[raw_base:raw_base + (last - first) * align])) != align * (last - first):
                         raise IOError(f'{self.fns[f]}: short read')
-            if self.format[f] in cd.CODECS:
+            if f in self.flac_index:
+                pass
+            elif self.format[f] in cd.CODECS:
                 spb, ch = self.spb[f], self.channels[f]
                 codec_rows.append((raw_base, last - first, scratch, cd.CODECS[self.format[f]], ch, align, spb))
                 by_rate_decoded.setdefault(self.rate[f], []).append(
@@ -486,8 +565,14 @@ class SegmentSource:
             seg_offset[o:o + (b - a)] = base + (k - a) * hop_len
             seg_valid[o:o + (b - a)] = np.clip(self.n_frames[f] - k * hop_len, 0, seg_len)
         by_rate = {rate: np.array(rows, dtype=ig.PIECE_DTYPE) for rate, rows in by_rate.items()}
+        flac = None
+        if by_rate_flac:
+            by_rate_flac = {rate: np.array(rows, dtype=ig.PIECE_DTYPE) for rate, rows in by_rate_flac.items()}
+            frames = np.concatenate(flac_rows) if flac_rows else np.zeros(0, fl.FRAME_DTYPE)
+            ids = np.concatenate(flac_ids) if flac_ids else np.zeros(0, np.int64)
+            flac = (fl.PrePass(frames, flac_scratch, self.flac_failed, ids), by_rate_flac)
         if not codec_rows:
-            return arena, used, seg_offset, seg_valid, ig.ChunkPieces(self.fs, by_rate, total)
+            return arena, used, seg_offset, seg_valid, ig.ChunkPieces(self.fs, by_rate, total, flac=flac)
         by_rate_decoded = {rate: np.array(rows, dtype=ig.PIECE_DTYPE) for rate, rows in by_rate_decoded.items()}
         prepass = cd.PrePass(np.array(codec_rows, dtype=cd.PIECE_DTYPE), scratch)
-        return arena, used, seg_offset, seg_valid, ig.ChunkPieces(self.fs, by_rate, total, prepass, by_rate_decoded)
+        return arena, used, seg_offset, seg_valid, ig.ChunkPieces(self.fs, by_rate, total, prepass, by_rate_decoded, flac=flac)

@@ -20,7 +20,8 @@ MAX_BLOCK_ALIGN = 4096
 
 
 def enabled():
-    return os.environ.get('NAFP_INGEST_CODECS', '') == '1'
+    # NAFP_INGEST_FLAC=1 (utils/flac.py) includes this switch
+    return os.environ.get('NAFP_INGEST_CODECS', '') == '1' or os.environ.get('NAFP_INGEST_FLAC', '') == '1'
 
 
 def samples_per_block(codec, channels, block_align):

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from ... import _lib
-from .audio_utils import n_segments, riff_scan, riff_scan_ex, _resample_on, _ingest_on, _codecs_on
+from .audio_utils import n_segments, riff_scan, riff_scan_ex, flac_scan, _resample_on, _ingest_on, _codecs_on, _flac_on, _taken_name
 
 MAX_IR_LENGTH = 600          # dataloader_keras.py:8
 
@@ -63,6 +63,10 @@ class PcmStore:
         self.n_frames, self.data_offset, self.start = [], [], []
         # NAFP_INGEST_ANY=1 (includes NAFP_RESAMPLE=1): any PCM / float format, 1 to 8 channels, rates in either direction
         # NAFP_INGEST_CODECS=1 (includes both): A-law, mu-law, IMA and MS ADPCM too; `spb` is the frames per block_align bytes
+        # NAFP_INGEST_FLAC=1 (includes all three): `.flac` names too; `flac_index[f]` is the file's frame index (utils/flac.py) and
+        # `flac_failed` counts, on the device, the frames that failed their checks while `.device()` decoded them
+        self.flac = _flac_on()
+        self.flac_index, self.flac_failed = {}, None
         self.codecs = _codecs_on()
         self.ingest = _ingest_on()
         self.resample = _resample_on() or self.ingest
@@ -70,11 +74,15 @@ class PcmStore:
         self.format, self.block_align, self.spb = [], [], []
         pos = int(base)
         for fn in self.fns:
-            if fn[-3:] != 'wav':
+            if not _taken_name(fn, self.flac):
                 raise NotImplementedError(fn[-3:])
             if self.ingest:
                 from . import ingest as ig
-                info = riff_scan_ex(fn, fs, codecs=True) if self.codecs else riff_scan_ex(fn, fs)
+                if fn[-3:] != 'wav':
+                    info = flac_scan(fn, fs)
+                    self.flac_index[len(self.n_frames)] = info['index']
+                else:
+                    info = riff_scan_ex(fn, fs, codecs=True) if self.codecs else riff_scan_ex(fn, fs)
                 rate, ch, off, nfr = info['rate'], info['channels'], info['offset'], info['n_frames']
                 native = ig.is_native(info, fs)
                 n_model = nfr if native else ig.n_out(nfr, rate, fs)
@@ -200,6 +208,8 @@ class PcmArena:
         uploads the byte range nafp_ingest_input_range x block_align) and one nafp_ingest_piece per run."""
         from . import ingest as ig
         from . import codecs as cd
+        if f in getattr(s, 'flac_index', {}):
+            return PcmArena._flac_file(s, f, d, stage)
         plan = ig.plan_for(s.rate[f], s.fs, d.device)
         align, n_in, n_total, start = int(s.block_align[f]), int(s.n_in[f]), int(s.n_frames[f]), int(s.start[f])
         codec = cd.CODECS.get(s.format[f])          # a codec file: whole blocks are uploaded and decoded into a scratch tensor first
@@ -233,6 +243,63 @@ class PcmArena:
                     raw, first, n_frames = pcm.view(torch.uint8), first * spb, min(n_frames * spb, n_in - first * spb)
                 piece = np.array([(0, first, n_frames, n_in, n0, start + n0, n1 - n0, s.channels[f], fmt, 0)], dtype=ig.PIECE_DTYPE)
                 plan.run(raw, piece, d)
+
+
+    @staticmethod
+    def _flac_file(s, f, d, stage):
+        """`_ingest_file` for a FLAC file (NAFP_INGEST_FLAC=1): each run uploads the WHOLE FRAMES that cover its input range, decodes
+        them into a byte scratch tensor (utils/flac.py) and ingests that as 16- or 24-bit PCM.  Frames that fail their checks are
+        zeros; each is counted once, on the device, in s.flac_failed."""
+        from . import ingest as ig
+        from . import flac as fl
+        idx = s.flac_index[f]
+        plan = ig.plan_for(s.rate[f], s.fs, d.device)
+        n_in, n_total, start, ch = int(s.n_in[f]), int(s.n_frames[f]), int(s.start[f]), int(s.channels[f])
+        fmt = ig.FORMATS['s16' if idx.bps <= 16 else 's24'][0]
+        stage_bytes = stage.numpy().view(np.uint8)
+        # outputs per run: the frames that cover their input span (two more than the span itself) fit the staging buffer at the
+        # file's mean bytes per sample, the largest frame counted twice
+        margin = 2 * (plan.half // plan.L + 2) + 2 * int(idx.block.max())
+        per_sample = max(1., float(idx.n_bytes.sum()) / max(int(idx.start[-1]), 1))
+        room = int((len(stage_bytes) - 2 * int(idx.n_bytes.max())) / (2 * per_sample)) - margin
+        if room * plan.L < plan.M:
+            raise NotImplementedError(f'{s.fns[f]}: staging buffer too small to convert FLAC from {s.rate[f]} Hz')
+        step = max(1, min(room * plan.L // plan.M, (1 << 31) - 1))
+        counted = 0
+        with open(s.fns[f], 'rb', buffering=0) as fh:
+            n0 = 0
+            while n0 < n_total:
+                n1 = min(n_total, n0 + step)
+                first, last = ig.input_range(n0, n1, n_in, s.rate[f], s.fs)
+                k0, k1 = fl.frame_range(idx, first, last)
+                rows, n_raw, n_pcm = fl.records(idx, k0, k1, 0, 0)
+                if n_raw > len(stage_bytes):             # denser than the file's mean: halve the run
+                    if n1 - n0 <= 1:
+                        raise NotImplementedError(f'{s.fns[f]}: staging buffer too small for its FLAC frames')
+                    step = max(1, (n1 - n0) // 2)
+                    continue
+                if n_raw:
+                    fh.seek(int(idx.offset[k0]))
+                    if fh.readinto(memoryview(stage_bytes[:n_raw])) != n_raw:
+                        raise IOError(f'{s.fns[f]}: short read')
+                raw = stage[:max((n_raw + 1) // 2, 1)].to(d.device, non_blocking=False).view(torch.uint8)
+                pcm = torch.empty((max(n_pcm, 1),), dtype=torch.uint8, device=d.device)
+                status = torch.zeros((max(k1 - k0, 1),), dtype=torch.int32, device=d.device)
+                fl.decode(raw, rows, pcm, status)
+                if s.flac_failed is None:
+                    s.flac_failed = torch.zeros((), dtype=torch.int64, device=d.device)
+                s.flac_failed += (status[max(counted - k0, 0):k1 - k0] != 0).sum()
+                counted = max(counted, k1)
+                frame0 = int(idx.start[k0]) if k1 > k0 else 0
+                covered = int(idx.start[k1] - idx.start[k0]) if k1 > k0 else 0
+                piece = np.array([(0, frame0, max(0, min(covered, n_in - frame0)), n_in, n0, start + n0, n1 - n0, ch, fmt, 0)],
+                                 dtype=ig.PIECE_DTYPE)
+                plan.run(raw if n_pcm == 0 else pcm, piece, d)
+                n0 = n1
+
+    def flac_failed_frames(self):
+        """Frames of the stores' FLAC files that failed their checks in `.device()` (one read of the device counters)."""
+        return sum(int(s.flac_failed.item()) for s in self.stores if getattr(s, 'flac_failed', None) is not None)
 
 
 def _randint(rng, low, high, size=None):

@@ -18,8 +18,8 @@ FORMATS = _lib.INGEST_FORMATS                      # name -> (NAFP_INGEST_* code
 
 
 def enabled():
-    # NAFP_INGEST_CODECS=1 (utils/codecs.py) includes this switch
-    return os.environ.get('NAFP_INGEST_ANY', '') == '1' or os.environ.get('NAFP_INGEST_CODECS', '') == '1'
+    # NAFP_INGEST_CODECS=1 (utils/codecs.py) and NAFP_INGEST_FLAC=1 (utils/flac.py) include this switch
+    return any(os.environ.get(k, '') == '1' for k in ('NAFP_INGEST_ANY', 'NAFP_INGEST_CODECS', 'NAFP_INGEST_FLAC'))
 
 
 def geometry(fs_in, fs_out):
@@ -122,11 +122,13 @@ class ChunkPieces:
     to the host piece array of that rate (native files ride along through the identity plan).  With NAFP_INGEST_CODECS=1 a
     launch may hold codec files: `prepass` (utils/codecs.PrePass) then decodes their blocks from the raw arena into an int16
     scratch tensor first, on the same stream, and `by_rate_decoded` holds the pieces (format s16) that index that tensor's
-    bytes."""
+    bytes.  With NAFP_INGEST_FLAC=1 it may hold FLAC files: `flac` = (utils/flac.PrePass, pieces by rate) is the same arrangement
+    with a byte scratch tensor of its own, its pieces of format s16 or s24."""
 
-    def __init__(self, fs_out, by_rate, out_total, prepass=None, by_rate_decoded=None):
+    def __init__(self, fs_out, by_rate, out_total, prepass=None, by_rate_decoded=None, flac=None):
         self.fs_out, self.by_rate, self.out_total = fs_out, by_rate, int(out_total)
         self.prepass, self.by_rate_decoded = prepass, by_rate_decoded or {}
+        self.flac = flac
 
     def run(self, raw_dev):
         """raw_dev: the uploaded arena, uint8 or an int16 tensor over the same bytes (the loaders' pinned buffers are int16)."""
@@ -138,6 +140,10 @@ class ChunkPieces:
         if self.prepass is not None:
             pcm = self.prepass.run(raw).view(torch.uint8)
             for fs_in, pieces in self.by_rate_decoded.items():
+                plan_for(fs_in, self.fs_out, raw.device).run(pcm, pieces, out)
+        if self.flac is not None:
+            pcm = self.flac[0].run(raw)
+            for fs_in, pieces in self.flac[1].items():
                 plan_for(fs_in, self.fs_out, raw.device).run(pcm, pieces, out)
         return out
 

@@ -12,6 +12,12 @@ alternating inside a rep so that drift hits them alike; median and range over th
      blocks, MS ADPCM 44.1 kHz stereo in 2048-byte blocks and IMA ADPCM 44.1 kHz mono in 4096-byte blocks -- blocks of random
      bytes: the decoders have no data-dependent loop -- next to two figures of the same launch: the 16-bit ingest of the samples
      it decoded, and the log-mel kernel.
+  4. the FLAC pre-pass (NAFP_INGEST_FLAC=1, csrc/flac.hip) of 44.1 kHz stereo 16-bit and 48 kHz stereo 24-bit in blocks of 4096 and
+     8 kHz mono 16-bit in blocks of 1152 -- LPC order 8, Rice-coded, music-like input from the writer of tests/_flac_ref.py (one
+     30-s file written once, every file of the launch holds its bytes: the decoder's loops ARE data-dependent) -- next to the
+     ingest of the PCM it decoded and the log-mel kernel; `prepass_all_failed` is the same launch with every record cut to 8
+     bytes, i.e. the launch overhead, the allocations and the store stage's zero fill without the serial stage; `index` is the
+     host's one pass over the file (nafp_flac_index_host), in MB/s.
 A launch is 640 one-second segments at a hop of 0.5 s: 320.5 s of audio, cut into 30-s files as generate would (11 pieces).
 One JSON line at the end."""
 import json
@@ -62,6 +68,31 @@ def codec_pieces(ig, cd, codec, fs_in, fs_out, ch, align):
         scratch += ((b1 - b0) * spb * ch + 7) // 8 * 8
         out_pos += (n_out + 7) // 8 * 8
     return np.array(c_rows, dtype=cd.PIECE_DTYPE), np.array(i_rows, dtype=ig.PIECE_DTYPE), raw_pos, scratch, out_pos
+
+
+def flac_launch(ig, fl, index, fs_in, fs_out, file_bytes):
+    """The launch of a FLAC tree as SegmentSource._ingest_chunk cuts it: per 30-s file the whole frames that cover the samples its
+    outputs read.  -> (frame records, ingest piece array, raw bytes, scratch bytes, outputs, [(raw offset, file byte range)])."""
+    total_out = (SEGMENTS - 1) * (fs_out // 2) + fs_out
+    n_in = int(index.start[-1])
+    f_rows, i_rows, copies, raw_pos, scratch, out_pos = [], [], [], 0, 0, 0
+    while out_pos < total_out:
+        n_out = min(ig.n_out(n_in, fs_in, fs_out), total_out - out_pos)
+        k0, k1 = fl.frame_range(index, *ig.input_range(0, n_out, n_in, fs_in, fs_out))
+        rows, n_raw, n_pcm = fl.records(index, k0, k1, raw_pos, scratch)
+        f_rows.append(rows)
+        copies.append((raw_pos, int(index.offset[k0]), n_raw))
+        covered = int(index.start[k1] - index.start[k0])
+        i_rows.append((scratch, int(index.start[k0]), min(covered, n_in - int(index.start[k0])), n_in, 0, out_pos, n_out, index.channels,
+                       ig.FORMATS['s16' if index.bps <= 16 else 's24'][0], 0))
+        raw_pos += (n_raw + 15) // 16 * 16
+        scratch += (n_pcm + 15) // 16 * 16
+        out_pos += (n_out + 7) // 8 * 8
+    raw = np.zeros(raw_pos, np.uint8)
+    data = np.frombuffer(file_bytes, np.uint8)
+    for at, off, n in copies:
+        raw[at:at + n] = data[off:off + n]
+    return np.concatenate(f_rows), np.array(i_rows, dtype=ig.PIECE_DTYPE), raw, scratch, out_pos
 
 
 def timed(fns):
@@ -171,6 +202,50 @@ def main():
                      'blocks_per_group': int(lib.nafp_codec_blocks_per_group(cd.CODECS[codec], ch, align)),
                      'prepass': t[0], 'ingest_s16': t[1], 'log_mel': t[2],
                      'prepass_over_ingest': round(t[0]['median_ms'] / t[1]['median_ms'], 3)}
+    # 4. the FLAC pre-pass next to the ingest of what it decoded and the log-mel of the same launch
+    import time
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import _flac_ref as fr
+    from neural_audio_fp_amd.model.utils import flac as fl
+    for name, fs_in, ch, bps, block in (('flac16_x2_44100_block4096', 44100, 2, 16, 4096), ('flac24_x2_48000_block4096', 48000, 2, 24, 4096),
+                                        ('flac16_x1_8000_block1152', 8000, 1, 16, 1152)):
+        x = fr.music(FILE_SECONDS * fs_in, fs_in, ch, bps, seed=bps + ch, scale=.5)
+        data = fr.write_stream(x, bps, fs_in, block=block, sub=fr.lpc_recipe(x[:fs_in, 0], 8, 12, porder=4, method=0)).data
+        t0 = time.perf_counter()
+        info, index = fl.scan(data)
+        t_index = time.perf_counter() - t0
+        idx = fl.Index(index, ch, bps, fs_in)
+        f_p, i_p, raw_np, scratch, n_out = flac_launch(ig, fl, idx, fs_in, 8000, data)
+        raw_bytes = len(raw_np)
+        raw = torch.from_numpy(raw_np).cuda()
+        pcm = torch.zeros((scratch,), dtype=torch.uint8, device='cuda')
+        out = torch.zeros((n_out,), dtype=torch.int16, device='cuda')
+        status = torch.zeros((len(f_p),), dtype=torch.int32, device='cuda')
+        fl.check_frames(f_p, raw_bytes, scratch)
+        ig.check_pieces(fs_in, 8000, i_p, scratch, n_out)
+        f_cut = f_p.copy()
+        f_cut['n_bytes'] = 8
+        d_f = torch.from_numpy(f_p.view(np.uint8).reshape(-1)).cuda()
+        d_cut = torch.from_numpy(f_cut.view(np.uint8).reshape(-1)).cuda()
+        d_i = torch.from_numpy(i_p.view(np.uint8).reshape(-1)).cuda()
+        plan = ig.plan_for(fs_in, 8000)
+        f_dec = lambda: _lib.check(lib.nafp_flac_decode(_lib.ptr(raw), raw_bytes, _lib.ptr(d_f), len(f_p), _lib.ptr(pcm), scratch,
+                                                        _lib.ptr(status), st), 'flac_decode')
+        f_fail = lambda: _lib.check(lib.nafp_flac_decode(_lib.ptr(raw), raw_bytes, _lib.ptr(d_cut), len(f_p), _lib.ptr(pcm), scratch,
+                                                         None, st), 'flac_decode')
+        f_ing = lambda: _lib.check(lib.nafp_ingest_i16(plan.handle, _lib.ptr(pcm), scratch, _lib.ptr(d_i), len(i_p), _lib.ptr(out), n_out,
+                                                       st), 'ingest_i16')
+        f_dec()
+        torch.cuda.synchronize()
+        assert int((status != 0).sum()) == 0, 'the measured launch must decode'
+        mel = mel_for(8000, out, n_out)
+        t = timed([f_dec, f_fail, f_ing, mel])
+        f_dec()                                                   # leave decoded PCM behind, not the zero fill
+        res[name] = {'frames': len(f_p), 'raw_bytes': int(raw_bytes), 'decoded_bytes': int(scratch), 'outputs': int(n_out),
+                     'file_bytes': len(data), 'bits_per_sample': round(8 * len(data) / x.size, 2),
+                     'index': {'seconds': round(t_index, 4), 'mb_per_s': round(len(data) / 1e6 / t_index, 1), 'frames': len(index)},
+                     'prepass': t[0], 'prepass_all_failed': t[1], 'ingest': t[2], 'log_mel': t[3],
+                     'prepass_over_ingest': round(t[0]['median_ms'] / t[2]['median_ms'], 3)}
     print(json.dumps(res))
 
 

@@ -11,15 +11,16 @@ Mirrors the parts of the reference's `Dataset` (model/dataset.py:10-323) that
 """
 import glob
 
-from .utils.audio_utils import SegmentSource, _flac_on
+from .utils.audio_utils import SegmentSource
 from .utils.dataloader_keras import genUnbalSequence
+from .utils.resample import switches
 
 
 def _audio_files(prefix):
     """sorted(glob(prefix + '*.wav')), as the reference lists a directory; under NAFP_INGEST_FLAC=1 the names ending in `.flac` (any
     letter case) are merged in and the whole list is sorted by path."""
     fps = glob.glob(prefix + '*.wav', recursive=True)
-    if _flac_on():
+    if switches().flac:
         fps += [p for p in glob.glob(prefix + '*', recursive=True) if p[-5:].lower() == '.flac']
     return sorted(fps)
 

@@ -356,7 +356,7 @@ class StreamedEmbedder:
         return self.h_pcm[k].numpy()
 
     def embed_windows(self, arena, used, seg_offset, seg_valid, group, pieces=None):
-        """`pieces` (utils/resample.ChunkPieces): `arena` holds raw frames at the files' own rates; they are resampled on this
+        """`pieces` (utils/ingest.ChunkPieces): `arena` holds the files' bytes as they are; they are decoded and resampled on this
         launch's stream into a device arena at the model rate, which the windows then index."""
         k = self.i % len(self.streams)
         self.i += 1
@@ -438,8 +438,7 @@ def generate_fingerprint(cfg, checkpoint_name, checkpoint_index, source_root_dir
             arr = np.memmap(path, dtype='float32', mode='r+', shape=arr_shape)
         print(f"=== Generating fingerprint from \x1b[1;32m'{key}'\x1b[0m bsz={bsz}, {n_items} items, d={dim} ===")
         files = getattr(ds[key], 'ev', ds[key])    # a synthesising sequence ('unseen_syn'): the store of its event files
-        if getattr(files, 'ingest', False):        # NAFP_INGEST_ANY=1: any PCM / float format, channel count and rate
-            # (NAFP_INGEST_CODECS=1 includes it: A-law, mu-law and ADPCM files are counted and named here too, e.g. '8000x1xalaw')
+        if getattr(files, 'ingest', False):        # NAFP_INGEST_ANY=1 and the layers above it: named by format too, e.g. '8000x1xalaw'
             from .utils.ingest import rates_summary
             source_rates[key] = rates_summary(files)
             print(f"'{key}': {source_rates[key]['resampled']} of {source_rates[key]['files']} files are decoded, mixed down and "

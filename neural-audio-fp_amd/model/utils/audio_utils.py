@@ -18,6 +18,11 @@ import wave
 
 import numpy as np
 
+from . import codecs as cd
+from . import flac as fl
+from . import ingest as ig
+from . import resample as rs
+
 
 def n_segments(n_frames, fs=8000, duration=1., hop=.5):
     """audio_utils.py:171-177."""
@@ -27,34 +32,44 @@ def n_segments(n_frames, fs=8000, duration=1., hop=.5):
     return 1
 
 
-def riff_scan(filename):
-    """Header scan of a RIFF/WAVE file WITHOUT reading the samples: (fs, channels, sample width in
-    bytes, byte offset of the first sample, frame count).  What `wave.open(...).getnframes()` reports
-    (audio_utils.py:160-169), plus where the data chunk starts, so that a sample range can be read
-    straight into a staging buffer."""
-    size = os.path.getsize(filename)
+def _riff_chunks(filename, keep=(b'fmt ',), fmt_min=0):
+    """Walk of a RIFF/WAVE file's chunks up to the data chunk, WITHOUT reading the samples: ([(id, declared size, body as stored,
+    pad byte included)] of the chunks named in `keep`, in file order; bytes of the data chunk that the file holds; byte offset of
+    the first sample).  fmt_min: a fmt chunk shorter than this is refused where it stands."""
     with open(filename, 'rb') as f:
         head = f.read(12)
         if len(head) < 12 or head[:4] != b'RIFF' or head[8:12] != b'WAVE':
             raise ValueError(f'{filename}: not a RIFF/WAVE file')
-        fmt = None
+        size = os.fstat(f.fileno()).st_size
+        chunks, seen_fmt, off = [], False, 12              # off: where the next chunk header stands (no tell() per file)
         while True:
             hdr = f.read(8)
             if len(hdr) < 8:
                 raise ValueError(f'{filename}: no data chunk')
             cid, csz = hdr[:4], struct.unpack('<I', hdr[4:])[0]
-            if cid == b'fmt ':
-                body = f.read(csz + (csz & 1))
-                tag, ch, rate, _, align, bits = struct.unpack('<HHIIHH', body[:16])
-                fmt = (tag, ch, rate, align, bits)
-            elif cid == b'data':
-                if fmt is None:
+            if cid == b'data':
+                if not seen_fmt:
                     raise ValueError(f'{filename}: data chunk before fmt chunk')
-                off = f.tell()
-                csz = min(csz, size - off)
-                return fmt[2], fmt[1], fmt[4] // 8, off, csz // fmt[3]
+                return chunks, min(csz, size - off - 8), off + 8
+            if cid in keep:
+                body = f.read(csz + (csz & 1))
+                if fmt_min and cid == b'fmt ' and min(csz, len(body)) < fmt_min:
+                    raise ValueError(f'{filename}: fmt chunk of {min(csz, len(body))} bytes')
+                chunks.append((cid, csz, body))
+                seen_fmt = seen_fmt or cid == b'fmt '
             else:
                 f.seek(csz + (csz & 1), 1)
+            off += 8 + csz + (csz & 1)
+
+
+def riff_scan(filename):
+    """Header scan of a RIFF/WAVE file WITHOUT reading the samples: (fs, channels, sample width in
+    bytes, byte offset of the first sample, frame count).  What `wave.open(...).getnframes()` reports
+    (audio_utils.py:160-169), plus where the data chunk starts, so that a sample range can be read
+    straight into a staging buffer."""
+    chunks, size, off = _riff_chunks(filename)
+    tag, ch, rate, _, align, bits = struct.unpack('<HHIIHH', chunks[-1][2][:16])          # the last fmt chunk before the data
+    return rate, ch, bits // 8, off, size // align
 
 
 _WAVE_TAGS = {0x0002: 'ADPCM', 0x0006: 'A-law', 0x0007: 'mu-law', 0x0011: 'IMA ADPCM', 0x0031: 'GSM 6.10', 0x0050: 'MPEG',
@@ -71,7 +86,6 @@ _MS_COEFS = (256, 0, 512, -256, 0, 0, 192, 64, 240, 0, 460, -208, 392, -232)
 def _codec_header(filename, fmt, tag, ch, align, bits):
     """The checks of a codec file's fmt chunk (riff_scan_ex with codecs=True): (format name, samples per block), or ValueError by
     name.  `tag` is the format tag, or for an extensible header the tag its sub-format GUID carries (6 or 7 only)."""
-    from . import codecs as cd
     name, title = _CODEC_TAGS[tag]
     if name in ('alaw', 'ulaw'):
         if bits != 8:
@@ -120,34 +134,13 @@ def riff_scan_ex(filename, fs=None, codecs=False):
     'ms4', 'width' 0, and the dict gains 'codec' (the same name; None for a PCM / float file) and 'samples_per_block' (spb; 1
     for a PCM / float file).  n_frames: whole = (data bytes // block_align) * spb, a trailing partial block ignored; a `fact`
     chunk whose first uint32 n satisfies 0 < n <= whole gives n_frames = n."""
-    size = os.path.getsize(filename)
     fact = None
-    with open(filename, 'rb') as f:
-        head = f.read(12)
-        if len(head) < 12 or head[:4] != b'RIFF' or head[8:12] != b'WAVE':
-            raise ValueError(f'{filename}: not a RIFF/WAVE file')
-        fmt = None
-        while True:
-            hdr = f.read(8)
-            if len(hdr) < 8:
-                raise ValueError(f'{filename}: no data chunk')
-            cid, csz = hdr[:4], struct.unpack('<I', hdr[4:])[0]
-            if cid == b'fmt ':
-                fmt = f.read(csz + (csz & 1))[:csz]
-                if len(fmt) < 16:
-                    raise ValueError(f'{filename}: fmt chunk of {len(fmt)} bytes')
-            elif cid == b'fact' and codecs:
-                body = f.read(csz + (csz & 1))[:csz]
-                if len(body) >= 4:
-                    fact, = struct.unpack('<I', body[:4])
-            elif cid == b'data':
-                if fmt is None:
-                    raise ValueError(f'{filename}: data chunk before fmt chunk')
-                off = f.tell()
-                csz = min(csz, size - off)
-                break
-            else:
-                f.seek(csz + (csz & 1), 1)
+    chunks, csz, off = _riff_chunks(filename, (b'fmt ', b'fact') if codecs else (b'fmt ',), fmt_min=16)
+    for cid, size, body in chunks:
+        if cid == b'fmt ':
+            fmt = body[:size]
+        elif size >= 4 and len(body) >= 4:
+            fact, = struct.unpack('<I', body[:4])
     tag, ch, rate, _, align, bits = struct.unpack('<HHIIHH', fmt[:16])
     if ch < 1 or ch > 8:
         raise ValueError(f'{filename}: {ch} channels; 1 to 8 are taken')
@@ -180,7 +173,6 @@ def riff_scan_ex(filename, fs=None, codecs=False):
     if codec is not None:
         name, spb = codec
         if fs is not None:
-            from . import ingest as ig
             ig.check_rate(rate, fs)
         whole = (csz // align) * spb
         return {'rate': rate, 'channels': ch, 'format': name, 'width': 0, 'block_align': align, 'offset': off,
@@ -192,7 +184,6 @@ def riff_scan_ex(filename, fs=None, codecs=False):
     if align != ch * width:
         raise ValueError(f'{filename}: block_align {align} != {ch} channels * {width} bytes per sample')
     if fs is not None:
-        from . import ingest as ig
         ig.check_rate(rate, fs)
     info = {'rate': rate, 'channels': ch, 'format': name, 'width': width, 'block_align': align, 'offset': off,
             'n_frames': csz // align}
@@ -209,7 +200,6 @@ def flac_scan(filename, fs=None):
     not above the indexed sum, otherwise the indexed sum.  Refused by name (ValueError): Ogg FLAC, no `fLaC` marker, a first
     metadata block that is not a 34-byte STREAMINFO, a depth other than 8 / 12 / 16 / 20 / 24 bits, a maximum block size above
     16384, a file without a valid frame, and with `fs` a rate that cannot be brought to fs."""
-    from . import flac as fl
     with open(filename, 'rb') as f:
         data = f.read()
     info, frames = fl.scan(data)
@@ -224,7 +214,6 @@ def flac_scan(filename, fs=None):
         raise ValueError(f'{filename}: no valid FLAC frame found')
     rate, ch, bps = int(info['rate']), int(info['channels']), int(info['bps'])
     if fs is not None:
-        from . import ingest as ig
         ig.check_rate(rate, fs)
     total, indexed = int(info['total_samples']), int(info['indexed_samples'])
     return {'rate': rate, 'channels': ch, 'format': f'flac{bps}', 'width': 0, 'block_align': 0, 'offset': 0,
@@ -273,28 +262,57 @@ def file_segments(pcm, fs=8000, duration=1., hop=.5):
     return pcm[idx]
 
 
-def _resample_on():
-    return os.environ.get('NAFP_RESAMPLE', '') == '1'
+class FileCatalog:
+    """The files of a loader, each header scanned ONCE (the reference re-opens per segment) under the opt-in layers the environment
+    sets (utils/resample.switches: the flags `resample`, `ingest`, `codecs`, `flac`).  `files[f]` is the whole entry
+    (ingest.FileEntry); the same as columns, one value per file: `n_frames` (the length at the model rate `fs`), `data_offset`,
+    and what describes the file itself, `rate`, `channels`, `n_in` (its frame count), `resampled` (the device converts it: not
+    16-bit mono at `fs`); with `ingest` also `format`, `block_align` and `spb` (frames per block_align bytes: 1 unless a codec).
+    `flac_index[f]` is the frame index of a FLAC file, built here by one pass over it, and `flac_failed` (flac.FailedFrames, None
+    without a FLAC file) collects on the device which of those frames failed their checks when decoded."""
+
+    def __init__(self, fns, fs):
+        self.fns, self.fs = list(fns), fs
+        self.resample, self.ingest, self.codecs, self.flac, _ = rs.switches()
+        rows, n_flac_frames = [], 0
+        for fn in self.fns:
+            if fn[-3:] != 'wav' and not (self.flac and fn[-5:].lower() == '.flac'):     # `.flac` in any letter case
+                raise NotImplementedError(fn[-3:])
+            if self.ingest:
+                info = flac_scan(fn, fs) if fn[-3:] != 'wav' else riff_scan_ex(fn, fs, codecs=self.codecs)
+                index = info.get('index')
+                kind = 'flac' if index is not None else 'codec' if info['format'] in cd.CODECS else 'pcm'
+                rate, ch, off, nfr = info['rate'], info['channels'], info['offset'], info['n_frames']
+                native = ig.is_native(info, fs)
+                n_model = nfr if native else ig.n_out(nfr, rate, fs)
+                fmt, align, spb = info['format'], info['block_align'], info.get('samples_per_block', 1)
+            else:
+                rate, ch, width, off, nfr = riff_scan(fn)
+                kind, index, fmt, align, spb = 'pcm16', None, 's16', 2 * ch, 1
+                if self.resample:
+                    rs.check_file(fn, rate, ch, width, fs)
+                    native = rate == fs and ch == 1
+                    n_model = nfr if native else rs.n_out(nfr, rate, fs)
+                else:
+                    if rate != fs:
+                        raise ValueError('Sample rate should be {} but got {}'.format(str(fs), str(rate)))
+                    if width != 2 or ch != 1:
+                        raise ValueError(f'{fn}: expected 16-bit mono PCM')
+                    native, n_model = True, nfr
+            rows.append((fn, kind, rate, ch, nfr, n_model, not native, off, fmt, align, spb, index, n_flac_frames))
+            if index is not None:
+                n_flac_frames += len(index)
+        self.files = list(map(ig.FileEntry._make, rows))
+        cols = dict(zip(ig.FileEntry._fields, map(list, zip(*self.files)))) if self.files else {k: [] for k in ig.FileEntry._fields}
+        for col in ('n_frames', 'data_offset', 'rate', 'channels', 'n_in', 'resampled'):
+            setattr(self, col, cols[col])
+        for col in ('format', 'block_align', 'spb'):
+            setattr(self, col, cols[col] if self.ingest else [])
+        self.flac_index = {f: index for f, index in enumerate(cols['flac']) if index is not None} if self.flac else {}
+        self.flac_failed = fl.FailedFrames([0 if index is None else len(index) for index in cols['flac']]) if self.flac_index else None
 
 
-def _flac_on():
-    return os.environ.get('NAFP_INGEST_FLAC', '') == '1'
-
-
-def _codecs_on():
-    return os.environ.get('NAFP_INGEST_CODECS', '') == '1' or _flac_on()           # NAFP_INGEST_FLAC=1 includes it
-
-
-def _taken_name(fn, flac):
-    """The loaders' name check: `wav`, and under NAFP_INGEST_FLAC=1 `.flac` in any letter case."""
-    return fn[-3:] == 'wav' or (flac and fn[-5:].lower() == '.flac')
-
-
-def _ingest_on():
-    return os.environ.get('NAFP_INGEST_ANY', '') == '1' or _codecs_on()          # NAFP_INGEST_CODECS=1 includes it
-
-
-class SegmentSource:
+class SegmentSource(FileCatalog):
     """Ordered segments of a list of WAV files, served in consecutive batches.
 
     Counterpart of `genUnbalSequence(fns, bsz, n_anchor=bsz, shuffle=False,
@@ -304,61 +322,10 @@ class SegmentSource:
     """
 
     def __init__(self, fns_list, bsz, duration=1., hop=.5, fs=8000):
-        self.fns, self.bsz, self.duration, self.hop, self.fs = list(fns_list), int(bsz), duration, hop, fs
+        super().__init__(fns_list, fs)
+        self.bsz, self.duration, self.hop = int(bsz), duration, hop
         self.seg_len = int(fs * duration)
         self.hop_len = int(np.floor(hop * fs))
-        self.n_frames, self.data_offset = [], []
-        # NAFP_RESAMPLE=1: files at other rates / in stereo are taken too and resampled on the device (utils/resample.py);
-        # n_frames is then the length at the model rate, n_in / rate / channels describe the file itself
-        # NAFP_INGEST_ANY=1 (includes the above): any PCM / float format, 1 to 8 channels, rates in either direction
-        # (utils/ingest.py); `format` / `block_align` then describe the file's samples, and the raw arena of a launch holds BYTES
-        # NAFP_INGEST_CODECS=1 (includes both): A-law, mu-law, IMA and MS ADPCM too (utils/codecs.py); `spb` is then the frames per
-        # block_align bytes (1 for PCM / float), n_in the file's frame count, and a launch decodes whole blocks in a pre-pass
-        # NAFP_INGEST_FLAC=1 (includes all three): `.flac` names too (utils/flac.py); `flac_index[f]` is then the file's frame index,
-        # built here by one pass over the file, and a launch decodes the whole frames that cover its samples in a pre-pass
-        self.flac = _flac_on()
-        self.flac_index = {}
-        self.codecs = _codecs_on()
-        self.ingest = _ingest_on()
-        self.resample = _resample_on() or self.ingest
-        self.rate, self.channels, self.n_in, self.resampled = [], [], [], []
-        self.format, self.block_align, self.spb = [], [], []
-        for fn in self.fns:                      # ONE header scan per file (the reference re-opens per segment)
-            if not _taken_name(fn, self.flac):
-                raise NotImplementedError(fn[-3:])
-            if self.ingest:
-                from . import ingest as ig
-                if fn[-3:] != 'wav':
-                    info = flac_scan(fn, fs)
-                    self.flac_index[len(self.n_frames)] = info['index']
-                else:
-                    info = riff_scan_ex(fn, fs, codecs=True) if self.codecs else riff_scan_ex(fn, fs)
-                rate, ch, off, nfr = info['rate'], info['channels'], info['offset'], info['n_frames']
-                native = ig.is_native(info, fs)
-                n_model = nfr if native else ig.n_out(nfr, rate, fs)
-                self.format.append(info['format']); self.block_align.append(info['block_align'])
-                self.spb.append(info.get('samples_per_block', 1))
-                self.n_frames.append(n_model); self.data_offset.append(off)
-                self.rate.append(rate); self.channels.append(ch); self.n_in.append(nfr); self.resampled.append(not native)
-                continue
-            rate, ch, width, off, nfr = riff_scan(fn)
-            if self.resample:
-                from . import resample as rs
-                rs.check_file(fn, rate, ch, width, fs)
-                native = rate == fs and ch == 1
-                n_model = nfr if native else rs.n_out(nfr, rate, fs)
-            else:
-                if rate != fs:
-                    raise ValueError('Sample rate should be {} but got {}'.format(str(fs), str(rate)))
-                if width != 2 or ch != 1:
-                    raise ValueError(f'{fn}: expected 16-bit mono PCM')
-                native, n_model = True, nfr
-            self.n_frames.append(n_model); self.data_offset.append(off)
-            self.rate.append(rate); self.channels.append(ch); self.n_in.append(nfr); self.resampled.append(not native)
-        self.flac_failed = None
-        if self.flac_index:                      # which frames failed their checks: one byte per frame, on the device
-            from . import flac as fl
-            self.flac_failed = fl.FailedFrames([len(self.flac_index[f]) if f in self.flac_index else 0 for f in range(len(self.fns))])
         counts = [n_segments(nfr, fs, duration, hop) for nfr in self.n_frames]
         self.file_first = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         self.n_samples = int(self.file_first[-1])
@@ -416,9 +383,9 @@ class SegmentSource:
             r = end
 
     def iter_windows(self, row0, row1, rows_per_chunk, alloc=None):
-        """Yield (start_row, n_rows, arena, used, seg_offset, seg_valid) -- with NAFP_RESAMPLE=1 a seventh item, the launch's
-        resampling work (utils/resample.ChunkPieces; with NAFP_INGEST_ANY=1 utils/ingest.ChunkPieces, the arena then holding the
-        files' bytes) or None for a launch of model-rate mono files -- over rows [row0, row1):
+        """Yield (start_row, n_rows, arena, used, seg_offset, seg_valid) -- with NAFP_RESAMPLE=1 (or a layer above it) a seventh
+        item, the launch's device work (utils/ingest.ChunkPieces, the arena then holding the files' bytes as they are) or None
+        for a launch of model-rate 16-bit mono files -- over rows [row0, row1):
         the PCM every row needs is read ONCE from each file (contiguous sample range, straight into
         `arena` = alloc(n_samples), e.g. pinned memory) and row i is the window
         arena[seg_offset[i] : seg_offset[i] + seg_len] with samples >= seg_valid[i] meaning zero --
@@ -439,140 +406,29 @@ class SegmentSource:
                 total += (s1 - s0 + 7) // 8 * 8                      # 16-B aligned piece starts
                 q += b - a
             if self.resample and any(self.resampled[p[0]] for p in pieces):
-                chunk = self._ingest_chunk if self.ingest else self._resample_chunk
-                yield (r, n) + chunk(pieces, n, total, alloc)
-                r = end
-                continue
-            arena = alloc(total) if alloc is not None else np.empty(max(total, 1), np.int16)
+                # a launch that holds a file to convert: the arena holds the files' BYTES as they are (ingest.plan_span per piece),
+                # seg_offset / seg_valid index the model-rate arena of `total` samples that the work fills on the device; files
+                # the loaders would read straight go the same way in such a launch (the identity plan copies them)
+                launch = ig.LaunchPlan(self.fs, self.flac_failed)
+                for f, a, b, s0, s1, base, o in pieces:
+                    launch.add(self.files[f], s0, s1, base)
+                reads, used, work = launch.reads, launch.raw_bytes // 2, (launch.work(total),)
+            else:
+                reads = [(self.fns[f], self.data_offset[f] + 2 * s0, 2 * (s1 - s0), 2 * base) for f, a, b, s0, s1, base, o in pieces]
+                used, work = total, ((None,) if self.resample else ())
+            arena = alloc(used) if alloc is not None else np.empty(max(used, 1), np.int16)
+            raw = arena.view(np.uint8)
+            for fn, file_off, n_bytes, at in reads:
+                if n_bytes:
+                    with open(fn, 'rb', buffering=0) as fh:
+                        fh.seek(file_off)
+                        if fh.readinto(memoryview(raw[at:at + n_bytes])) != n_bytes:
+                            raise IOError(f'{fn}: short read')
             seg_offset = np.empty(n, np.int64)
             seg_valid = np.empty(n, np.int32)
             for f, a, b, s0, s1, base, o in pieces:
-                if s1 > s0:
-                    with open(self.fns[f], 'rb', buffering=0) as fh:
-                        fh.seek(self.data_offset[f] + 2 * s0)
-                        dst = memoryview(arena[base:base + (s1 - s0)]).cast('B')
-                        got = fh.readinto(dst)
-                        if got != 2 * (s1 - s0):
-                            raise IOError(f'{self.fns[f]}: short read')
                 k = np.arange(a, b, dtype=np.int64)
                 seg_offset[o:o + (b - a)] = base + (k - a) * hop_len
                 seg_valid[o:o + (b - a)] = np.clip(self.n_frames[f] - k * hop_len, 0, seg_len)
-            if self.resample:
-                yield r, n, arena, total, seg_offset, seg_valid, None
-            else:
-                yield r, n, arena, total, seg_offset, seg_valid
+            yield (r, n, arena, used, seg_offset, seg_valid) + work
             r = end
-
-    def _resample_chunk(self, pieces, n, total, alloc):
-        """A launch that holds a file to resample: (raw arena, used, seg_offset, seg_valid, ChunkPieces).  `arena` then holds the
-        RAW frames every piece's outputs read (nafp_resample_input_range; interleaved for stereo; 16-B aligned piece starts) and
-        seg_offset / seg_valid index the model-rate arena of `total` samples that ChunkPieces.run fills on the device.  Files
-        at the model rate in mono go the same way in such a launch (the identity plan copies them)."""
-        from . import resample as rs
-        seg_len, hop_len = self.seg_len, self.hop_len
-        raw_total, spans = 0, []
-        for f, a, b, s0, s1, base, o in pieces:
-            first, last = rs.input_range(s0, s1, self.n_in[f], self.rate[f], self.fs) if s1 > s0 else (0, 0)
-            spans.append((first, last, raw_total))
-            raw_total += ((last - first) * self.channels[f] + 7) // 8 * 8
-        arena = alloc(raw_total) if alloc is not None else np.empty(max(raw_total, 1), np.int16)
-        seg_offset = np.empty(n, np.int64)
-        seg_valid = np.empty(n, np.int32)
-        by_rate = {}
-        for (f, a, b, s0, s1, base, o), (first, last, raw_base) in zip(pieces, spans):
-            ch = self.channels[f]
-            if last > first:
-                with open(self.fns[f], 'rb', buffering=0) as fh:
-                    fh.seek(self.data_offset[f] + 2 * ch * first)
-                    dst = memoryview(arena[raw_base:raw_base + (last - first) * ch]).cast('B')
-                    if fh.readinto(dst) != 2 * ch * (last - first):
-                        raise IOError(f'{self.fns[f]}: short read')
-            by_rate.setdefault(self.rate[f], []).append((raw_base, first, last - first, self.n_in[f], s0, base, s1 - s0, ch))
-            k = np.arange(a, b, dtype=np.int64)
-            seg_offset[o:o + (b - a)] = base + (k - a) * hop_len
-            seg_valid[o:o + (b - a)] = np.clip(self.n_frames[f] - k * hop_len, 0, seg_len)
-        by_rate = {rate: np.array(rows, dtype=rs.PIECE_DTYPE) for rate, rows in by_rate.items()}
-        return arena, raw_total, seg_offset, seg_valid, rs.ChunkPieces(self.fs, by_rate, total)
-
-    def _ingest_chunk(self, pieces, n, total, alloc):
-        """`_resample_chunk` for NAFP_INGEST_ANY=1: (raw arena, used, seg_offset, seg_valid, ingest.ChunkPieces).  `arena` (int16
-        units, as `alloc` hands it out; `used` counts them) holds the files' BYTES: for every piece the byte range
-        nafp_ingest_input_range x block_align, read as the file has it, piece starts 16-B aligned.  seg_offset / seg_valid index
-        the model-rate arena of `total` samples, unchanged.  Native files go the same way in such a launch (identity plan).
-        A codec file (NAFP_INGEST_CODECS=1) uploads the WHOLE BLOCKS that cover its frame range; the launch's pre-pass
-        (codecs.PrePass) decodes them into an int16 scratch tensor and the file's ingest piece indexes that tensor as 16-bit PCM.
-        A FLAC file (NAFP_INGEST_FLAC=1) uploads the WHOLE FRAMES that cover its sample range, one contiguous byte range of the
-        file; flac.PrePass decodes them into a byte scratch tensor of its own, indexed as 16- or 24-bit PCM."""
-        from . import ingest as ig
-        from . import codecs as cd
-        from . import flac as fl
-        seg_len, hop_len = self.seg_len, self.hop_len
-        raw_bytes, spans = 0, []
-        for f, a, b, s0, s1, base, o in pieces:
-            first, last = ig.input_range(s0, s1, self.n_in[f], self.rate[f], self.fs) if s1 > s0 else (0, 0)
-            if f in self.flac_index:                 # samples -> the frames that hold them; their bytes
-                first, last = fl.frame_range(self.flac_index[f], first, last)
-                spans.append((first, last, raw_bytes))
-                raw_bytes += (fl.records(self.flac_index[f], first, last, 0, 0)[1] + 15) // 16 * 16
-                continue
-            if self.format[f] in cd.CODECS:          # frames -> the blocks that hold them
-                first, last = cd.block_range(first, last, self.spb[f])
-            spans.append((first, last, raw_bytes))
-            raw_bytes += ((last - first) * self.block_align[f] + 15) // 16 * 16
-        used = raw_bytes // 2
-        arena = alloc(used) if alloc is not None else np.empty(max(used, 1), np.int16)
-        raw = arena.view(np.uint8)
-        seg_offset = np.empty(n, np.int64)
-        seg_valid = np.empty(n, np.int32)
-        by_rate, by_rate_decoded, codec_rows, scratch = {}, {}, [], 0
-        by_rate_flac, flac_rows, flac_ids, flac_scratch = {}, [], [], 0
-        for (f, a, b, s0, s1, base, o), (first, last, raw_base) in zip(pieces, spans):
-            align = self.block_align[f]
-            if f in self.flac_index:
-                idx = self.flac_index[f]
-                rows, n_raw, n_pcm = fl.records(idx, first, last, raw_base, flac_scratch)
-                if n_raw:
-                    with open(self.fns[f], 'rb', buffering=0) as fh:
-                        fh.seek(int(idx.offset[first]))
-                        if fh.readinto(memoryview(raw[raw_base:raw_base + n_raw])) != n_raw:
-                            raise IOError(f'{self.fns[f]}: short read')
-                    flac_rows.append(rows)
-                    flac_ids.append(self.flac_failed.base[f] + np.arange(first, last, dtype=np.int64))
-                frame0 = int(idx.start[first]) if last > first else 0
-                covered = int(idx.start[last] - idx.start[first]) if last > first else 0
-                by_rate_flac.setdefault(self.rate[f], []).append(
-                    (flac_scratch, frame0, max(0, min(covered, self.n_in[f] - frame0)), self.n_in[f], s0, base, s1 - s0, self.channels[f],
-                     ig.FORMATS['s16' if idx.bps <= 16 else 's24'][0], 0))
-                flac_scratch += (n_pcm + 15) // 16 * 16
-            elif last > first:
-                with open(self.fns[f], 'rb', buffering=0) as fh:
-                    fh.seek(self.data_offset[f] + align * first)
-                    if fh.readinto(memoryview(raw[raw_base:raw_base + (last - first) * align])) != align * (last - first):
-                        raise IOError(f'{self.fns[f]}: short read')
-            if f in self.flac_index:
-                pass
-            elif self.format[f] in cd.CODECS:
-                spb, ch = self.spb[f], self.channels[f]
-                codec_rows.append((raw_base, last - first, scratch, cd.CODECS[self.format[f]], ch, align, spb))
-                by_rate_decoded.setdefault(self.rate[f], []).append(
-                    (2 * scratch, first * spb, min((last - first) * spb, self.n_in[f] - first * spb), self.n_in[f], s0, base, s1 - s0,
-                     ch, ig.FORMATS['s16'][0], 0))
-                scratch += ((last - first) * spb * ch + 7) // 8 * 8
-            else:
-                by_rate.setdefault(self.rate[f], []).append((raw_base, first, last - first, self.n_in[f], s0, base, s1 - s0,
-                                                             self.channels[f], ig.FORMATS[self.format[f]][0], 0))
-            k = np.arange(a, b, dtype=np.int64)
-            seg_offset[o:o + (b - a)] = base + (k - a) * hop_len
-            seg_valid[o:o + (b - a)] = np.clip(self.n_frames[f] - k * hop_len, 0, seg_len)
-        by_rate = {rate: np.array(rows, dtype=ig.PIECE_DTYPE) for rate, rows in by_rate.items()}
-        flac = None
-        if by_rate_flac:
-            by_rate_flac = {rate: np.array(rows, dtype=ig.PIECE_DTYPE) for rate, rows in by_rate_flac.items()}
-            frames = np.concatenate(flac_rows) if flac_rows else np.zeros(0, fl.FRAME_DTYPE)
-            ids = np.concatenate(flac_ids) if flac_ids else np.zeros(0, np.int64)
-            flac = (fl.PrePass(frames, flac_scratch, self.flac_failed, ids), by_rate_flac)
-        if not codec_rows:
-            return arena, used, seg_offset, seg_valid, ig.ChunkPieces(self.fs, by_rate, total, flac=flac)
-        by_rate_decoded = {rate: np.array(rows, dtype=ig.PIECE_DTYPE) for rate, rows in by_rate_decoded.items()}
-        prepass = cd.PrePass(np.array(codec_rows, dtype=cd.PIECE_DTYPE), scratch)
-        return arena, used, seg_offset, seg_valid, ig.ChunkPieces(self.fs, by_rate, total, prepass, by_rate_decoded, flac=flac)

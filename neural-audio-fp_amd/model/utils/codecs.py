@@ -1,18 +1,17 @@
 """Block codecs in WAV files -- G.711 A-law / mu-law, IMA ADPCM and MS ADPCM at 4 bits: host side of `nafp_codec_*`
 (include/nafp.h).
 
-Opt-in: NAFP_INGEST_CODECS=1.  It includes everything NAFP_INGEST_ANY=1 does (utils/ingest.py), and with it NAFP_RESAMPLE=1;
-setting it together with either is the same as setting it alone.  Without it every loader refuses these files by name, as before.
+Opt-in: NAFP_INGEST_CODECS=1 (the layers: utils/resample.switches).  Without it every loader refuses these files by name, as before.
 A codec file is decoded on the device only (csrc/codec.hip, exact integer arithmetic): a pre-pass turns the WHOLE BLOCKS that
 cover a frame range into interleaved 16-bit PCM in a scratch tensor, and the general ingest then reads that tensor as 16-bit
 PCM.  There is no CPU path, so whatever materialises samples on the host raises for such a file.
 """
 import ctypes
-import os
 
 import numpy as np
 
 from ... import _lib
+from .resample import switches
 
 PIECE_DTYPE = np.dtype(_lib.CODEC_PIECE_DTYPE)
 CODECS = _lib.CODECS                               # format name -> NAFP_CODEC_* code
@@ -20,8 +19,7 @@ MAX_BLOCK_ALIGN = 4096
 
 
 def enabled():
-    # NAFP_INGEST_FLAC=1 (utils/flac.py) includes this switch
-    return os.environ.get('NAFP_INGEST_CODECS', '') == '1' or os.environ.get('NAFP_INGEST_FLAC', '') == '1'
+    return switches().codecs
 
 
 def samples_per_block(codec, channels, block_align):

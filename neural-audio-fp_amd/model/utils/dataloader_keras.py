@@ -26,7 +26,8 @@ import numpy as np
 import torch
 
 from ... import _lib
-from .audio_utils import n_segments, riff_scan, riff_scan_ex, flac_scan, _resample_on, _ingest_on, _codecs_on, _flac_on, _taken_name
+from . import ingest as ig
+from .audio_utils import FileCatalog, n_segments
 
 MAX_IR_LENGTH = 600          # dataloader_keras.py:8
 
@@ -51,83 +52,41 @@ def segment_table(n_frames, fs, duration, hop, mode='all'):
     return out
 
 
-class PcmStore:
-    """All samples of a list of 16-bit mono WAV files in ONE int16 array: `start[f]` (first sample of
-    file f, 8-sample aligned), `n_frames[f]`.  `.host()` materialises it in numpy (tests, small sets),
-    `.device()` uploads it once through a pinned staging buffer.  With NAFP_RESAMPLE=1 files at other rates / in stereo are
-    taken too (utils/resample.py): `n_frames` / `start` then count samples at `fs`, `.device()` resamples such a file into its
-    place on the device and `.host()` raises (there is no CPU resampler)."""
+class PcmStore(FileCatalog):
+    """All samples of a list of WAV files in ONE int16 array at the model rate: the catalog of the files (audio_utils.FileCatalog,
+    with `n_frames` as an int64 array) plus their placement, `start[f]` (first sample of file f, 8-sample aligned) from `base` to
+    `end`.  `.host()` materialises it in numpy (tests, small sets), `.device()` uploads it once through a pinned staging buffer.
+    A file the device converts (`resampled[f]`, under the opt-in layers) is converted into its place by `.device()`; `.host()`
+    raises for it (there is no CPU path)."""
 
     def __init__(self, fns, fs, base=0):
-        self.fns, self.fs = list(fns), fs
-        self.n_frames, self.data_offset, self.start = [], [], []
-        # NAFP_INGEST_ANY=1 (includes NAFP_RESAMPLE=1): any PCM / float format, 1 to 8 channels, rates in either direction
-        # NAFP_INGEST_CODECS=1 (includes both): A-law, mu-law, IMA and MS ADPCM too; `spb` is the frames per block_align bytes
-        # NAFP_INGEST_FLAC=1 (includes all three): `.flac` names too; `flac_index[f]` is the file's frame index (utils/flac.py) and
-        # `flac_failed` counts, on the device, the frames that failed their checks while `.device()` decoded them
-        self.flac = _flac_on()
-        self.flac_index, self.flac_failed = {}, None
-        self.codecs = _codecs_on()
-        self.ingest = _ingest_on()
-        self.resample = _resample_on() or self.ingest
-        self.rate, self.channels, self.n_in, self.resampled = [], [], [], []
-        self.format, self.block_align, self.spb = [], [], []
-        pos = int(base)
-        for fn in self.fns:
-            if not _taken_name(fn, self.flac):
-                raise NotImplementedError(fn[-3:])
-            if self.ingest:
-                from . import ingest as ig
-                if fn[-3:] != 'wav':
-                    info = flac_scan(fn, fs)
-                    self.flac_index[len(self.n_frames)] = info['index']
-                else:
-                    info = riff_scan_ex(fn, fs, codecs=True) if self.codecs else riff_scan_ex(fn, fs)
-                rate, ch, off, nfr = info['rate'], info['channels'], info['offset'], info['n_frames']
-                native = ig.is_native(info, fs)
-                n_model = nfr if native else ig.n_out(nfr, rate, fs)
-                self.format.append(info['format']); self.block_align.append(info['block_align'])
-                self.spb.append(info.get('samples_per_block', 1))
-                self.n_frames.append(n_model); self.data_offset.append(off); self.start.append(pos)
-                self.rate.append(rate); self.channels.append(ch); self.n_in.append(nfr); self.resampled.append(not native)
-                pos += (n_model + 7) // 8 * 8
-                continue
-            rate, ch, width, off, nfr = riff_scan(fn)
-            if self.resample:
-                from . import resample as rs
-                rs.check_file(fn, rate, ch, width, fs)
-                native = rate == fs and ch == 1
-                n_model = nfr if native else rs.n_out(nfr, rate, fs)
-            else:
-                if rate != fs:
-                    raise ValueError('Sample rate should be {} but got {}'.format(str(fs), str(rate)))
-                if width != 2 or ch != 1:
-                    raise ValueError(f'{fn}: expected 16-bit mono PCM')
-                native, n_model = True, nfr
-            self.n_frames.append(n_model); self.data_offset.append(off); self.start.append(pos)
-            self.rate.append(rate); self.channels.append(ch); self.n_in.append(nfr); self.resampled.append(not native)
-            pos += (n_model + 7) // 8 * 8
-        self.base, self.end = int(base), pos
+        super().__init__(fns, fs)
         self.n_frames = np.asarray(self.n_frames, np.int64)
-        self.start = np.asarray(self.start, np.int64)
+        sizes = (self.n_frames + 7) // 8 * 8
+        self.start = int(base) + np.cumsum(sizes) - sizes
+        self.base, self.end = int(base), int(base) + int(sizes.sum())
 
-    def read_into(self, dst):
-        """dst: int16 numpy view of [base, end) (zero-initialised by the caller)."""
-        for f, fn in enumerate(self.fns):
-            n = int(self.n_frames[f])
-            if self.resampled[f] and getattr(self, 'ingest', False):
-                raise NotImplementedError(f'{fn}: {self.rate[f]} Hz x {self.channels[f]} x {self.format[f]} is decoded and resampled '
+    def read_into(self, dst, f0=0, f1=None, leave_converted=False):
+        """dst: int16 numpy view (zero-initialised by the caller) of the places of the files [f0, f1) (default: all, [base, end)).
+        leave_converted: a file the device converts stays zero instead of raising."""
+        f1 = len(self.fns) if f1 is None else f1
+        for f in range(f0, f1):
+            e = self.files[f]
+            if e.resampled and leave_converted:
+                continue
+            if e.resampled and self.ingest:
+                raise NotImplementedError(f'{e.fn}: {e.rate} Hz x {e.channels} x {e.format} is decoded and resampled '
                                           'on the device only (PcmArena.device); there is no CPU path')
-            if self.resampled[f]:
-                raise NotImplementedError(f'{fn}: {self.rate[f]} Hz x {self.channels[f]} is resampled on the device only '
+            if e.resampled:
+                raise NotImplementedError(f'{e.fn}: {e.rate} Hz x {e.channels} is resampled on the device only '
                                           '(PcmArena.device); there is no CPU resampler')
-            if n:
-                with open(fn, 'rb', buffering=0) as fh:
-                    fh.seek(self.data_offset[f])
-                    a = int(self.start[f] - self.base)
-                    got = fh.readinto(memoryview(dst[a:a + n]).cast('B'))
-                    if got != 2 * n:
-                        raise IOError(f'{fn}: short read')
+            if e.n_frames:
+                with open(e.fn, 'rb', buffering=0) as fh:
+                    fh.seek(e.data_offset)
+                    a = int(self.start[f] - self.start[f0])
+                    got = fh.readinto(memoryview(dst[a:a + e.n_frames]).cast('B'))
+                    if got != 2 * e.n_frames:
+                        raise IOError(f'{e.fn}: short read')
 
 
 class PcmArena:
@@ -161,145 +120,36 @@ class PcmArena:
                 a1 = int(s.start[g - 1]) + (int(s.n_frames[g - 1]) + 7) // 8 * 8
                 buf = stage.numpy()[:a1 - a0]
                 buf[:] = 0
-                sub = PcmStore.__new__(PcmStore)
-                sub.fns, sub.n_frames, sub.data_offset, sub.start, sub.base = s.fns[f:g], s.n_frames[f:g], s.data_offset[f:g], s.start[f:g], a0
-                # files to resample leave their place zero here and are filled below
-                sub.resampled = [False] * (g - f)
-                sub.n_frames = np.where(np.asarray(s.resampled[f:g], bool), 0, sub.n_frames)
-                sub.read_into(buf)
+                s.read_into(buf, f, g, leave_converted=True)     # files to convert leave their place zero here and are filled below
                 d[a0:a1].copy_(stage[:a1 - a0], non_blocking=False)
                 f = g
             for f in range(len(s.fns)):
                 if s.resampled[f]:
-                    (self._ingest_file if s.ingest else self._resample_file)(s, f, d, stage)
+                    self._convert_file(s, f, d, stage)
         if any(any(s.resampled) for s in self.stores):
             torch.cuda.current_stream(device).synchronize()
         return d
 
     @staticmethod
-    def _resample_file(s, f, d, stage):
-        """File f of store s -> d[start[f] : start[f] + n_frames[f]] at the model rate: its raw frames go through the staging
-        buffer in runs of outputs (each run uploads the frames it reads, nafp_resample_input_range) and one piece per run."""
-        from . import resample as rs
-        plan = rs.plan_for(s.rate[f], s.fs, d.device)
-        ch, n_in, n_total, start = s.channels[f], int(s.n_in[f]), int(s.n_frames[f]), int(s.start[f])
-        # outputs per run: their input span (n M / L frames + the filter's two half-widths) fits the staging buffer
-        margin = 2 * (plan.half // plan.L + 2)
-        room = stage.shape[0] // ch - margin
-        if room * plan.L < plan.M:
-            raise NotImplementedError(f'{s.fns[f]}: staging buffer too small to resample from {s.rate[f]} Hz')
-        step = max(1, min(room * plan.L // plan.M, (1 << 31) - 1))
-        with open(s.fns[f], 'rb', buffering=0) as fh:
-            for n0 in range(0, n_total, step):
-                n1 = min(n_total, n0 + step)
-                first, last = rs.input_range(n0, n1, n_in, s.rate[f], s.fs)
-                k = (last - first) * ch
-                if k:
-                    fh.seek(s.data_offset[f] + 2 * ch * first)
-                    if fh.readinto(memoryview(stage.numpy()[:k]).cast('B')) != 2 * k:
-                        raise IOError(f'{s.fns[f]}: short read')
-                raw = stage[:max(k, 1)].to(d.device, non_blocking=False)
-                piece = np.array([(0, first, last - first, n_in, n0, start + n0, n1 - n0, ch)], dtype=rs.PIECE_DTYPE)
-                plan.run(raw, piece, d)
-
-    @staticmethod
-    def _ingest_file(s, f, d, stage):
-        """`_resample_file` for NAFP_INGEST_ANY=1: the file's BYTES go through the staging buffer in runs of outputs (each run
-        uploads the byte range nafp_ingest_input_range x block_align) and one nafp_ingest_piece per run."""
-        from . import ingest as ig
-        from . import codecs as cd
-        if f in getattr(s, 'flac_index', {}):
-            return PcmArena._flac_file(s, f, d, stage)
-        plan = ig.plan_for(s.rate[f], s.fs, d.device)
-        align, n_in, n_total, start = int(s.block_align[f]), int(s.n_in[f]), int(s.n_frames[f]), int(s.start[f])
-        codec = cd.CODECS.get(s.format[f])          # a codec file: whole blocks are uploaded and decoded into a scratch tensor first
-        spb = int(s.spb[f]) if codec else 1
-        fmt = ig.FORMATS['s16' if codec else s.format[f]][0]
+    def _convert_file(s, f, d, stage):
+        """File f of store s -> d[start[f] : start[f] + n_frames[f]] at the model rate: its bytes go through the staging buffer in
+        runs of outputs (ingest.file_runs: each run uploads the one byte range its outputs need -- frames, whole codec blocks or
+        whole FLAC frames) and every run is a launch of one piece.  FLAC frames that fail their checks are zeros; each is counted
+        once, on the device, in s.flac_failed."""
         stage_bytes = stage.numpy().view(np.uint8)
-        # outputs per run: their input span (n M / L frames + the filter's two half-widths) fits the staging buffer (a codec
-        # file's span is rounded out to whole blocks: two more)
-        margin = 2 * (plan.half // plan.L + 2)
-        room = (len(stage_bytes) // align - (2 if codec else 0)) * spb - margin
-        if room * plan.L < plan.M:
-            raise NotImplementedError(f'{s.fns[f]}: staging buffer too small to convert from {s.rate[f]} Hz')
-        step = max(1, min(room * plan.L // plan.M, (1 << 31) - 1))
         with open(s.fns[f], 'rb', buffering=0) as fh:
-            for n0 in range(0, n_total, step):
-                n1 = min(n_total, n0 + step)
-                first, last = ig.input_range(n0, n1, n_in, s.rate[f], s.fs)
-                if codec:
-                    first, last = cd.block_range(first, last, spb)
-                k = (last - first) * align
-                if k:
-                    fh.seek(s.data_offset[f] + align * first)
-                    if fh.readinto(memoryview(stage_bytes[:k])) != k:
-                        raise IOError(f'{s.fns[f]}: short read')
-                raw = stage[:max((k + 1) // 2, 1)].to(d.device, non_blocking=False).view(torch.uint8)
-                n_frames = last - first
-                if codec:
-                    ch = s.channels[f]
-                    pcm = torch.empty((max(n_frames * spb * ch, 1),), dtype=torch.int16, device=d.device)
-                    cd.decode(raw, np.array([(0, n_frames, 0, codec, ch, align, spb)], dtype=cd.PIECE_DTYPE), pcm)
-                    raw, first, n_frames = pcm.view(torch.uint8), first * spb, min(n_frames * spb, n_in - first * spb)
-                piece = np.array([(0, first, n_frames, n_in, n0, start + n0, n1 - n0, s.channels[f], fmt, 0)], dtype=ig.PIECE_DTYPE)
-                plan.run(raw, piece, d)
-
-
-    @staticmethod
-    def _flac_file(s, f, d, stage):
-        """`_ingest_file` for a FLAC file (NAFP_INGEST_FLAC=1): each run uploads the WHOLE FRAMES that cover its input range, decodes
-        them into a byte scratch tensor (utils/flac.py) and ingests that as 16- or 24-bit PCM.  Frames that fail their checks are
-        zeros; each is counted once, on the device, in s.flac_failed."""
-        from . import ingest as ig
-        from . import flac as fl
-        idx = s.flac_index[f]
-        plan = ig.plan_for(s.rate[f], s.fs, d.device)
-        n_in, n_total, start, ch = int(s.n_in[f]), int(s.n_frames[f]), int(s.start[f]), int(s.channels[f])
-        fmt = ig.FORMATS['s16' if idx.bps <= 16 else 's24'][0]
-        stage_bytes = stage.numpy().view(np.uint8)
-        # outputs per run: the frames that cover their input span (two more than the span itself) fit the staging buffer at the
-        # file's mean bytes per sample, the largest frame counted twice
-        margin = 2 * (plan.half // plan.L + 2) + 2 * int(idx.block.max())
-        per_sample = max(1., float(idx.n_bytes.sum()) / max(int(idx.start[-1]), 1))
-        room = int((len(stage_bytes) - 2 * int(idx.n_bytes.max())) / (2 * per_sample)) - margin
-        if room * plan.L < plan.M:
-            raise NotImplementedError(f'{s.fns[f]}: staging buffer too small to convert FLAC from {s.rate[f]} Hz')
-        step = max(1, min(room * plan.L // plan.M, (1 << 31) - 1))
-        counted = 0
-        with open(s.fns[f], 'rb', buffering=0) as fh:
-            n0 = 0
-            while n0 < n_total:
-                n1 = min(n_total, n0 + step)
-                first, last = ig.input_range(n0, n1, n_in, s.rate[f], s.fs)
-                k0, k1 = fl.frame_range(idx, first, last)
-                rows, n_raw, n_pcm = fl.records(idx, k0, k1, 0, 0)
-                if n_raw > len(stage_bytes):             # denser than the file's mean: halve the run
-                    if n1 - n0 <= 1:
-                        raise NotImplementedError(f'{s.fns[f]}: staging buffer too small for its FLAC frames')
-                    step = max(1, (n1 - n0) // 2)
-                    continue
-                if n_raw:
-                    fh.seek(int(idx.offset[k0]))
-                    if fh.readinto(memoryview(stage_bytes[:n_raw])) != n_raw:
-                        raise IOError(f'{s.fns[f]}: short read')
-                raw = stage[:max((n_raw + 1) // 2, 1)].to(d.device, non_blocking=False).view(torch.uint8)
-                pcm = torch.empty((max(n_pcm, 1),), dtype=torch.uint8, device=d.device)
-                status = torch.zeros((max(k1 - k0, 1),), dtype=torch.int32, device=d.device)
-                fl.decode(raw, rows, pcm, status)
-                if s.flac_failed is None:
-                    s.flac_failed = torch.zeros((), dtype=torch.int64, device=d.device)
-                s.flac_failed += (status[max(counted - k0, 0):k1 - k0] != 0).sum()
-                counted = max(counted, k1)
-                frame0 = int(idx.start[k0]) if k1 > k0 else 0
-                covered = int(idx.start[k1] - idx.start[k0]) if k1 > k0 else 0
-                piece = np.array([(0, frame0, max(0, min(covered, n_in - frame0)), n_in, n0, start + n0, n1 - n0, ch, fmt, 0)],
-                                 dtype=ig.PIECE_DTYPE)
-                plan.run(raw if n_pcm == 0 else pcm, piece, d)
-                n0 = n1
+            for n0, n1, run in ig.file_runs(s.files[f], s.fs, int(s.start[f]), len(stage_bytes), s.flac_failed):
+                (fn, file_off, n_bytes, _), = run.reads
+                if n_bytes:
+                    fh.seek(file_off)
+                    if fh.readinto(memoryview(stage_bytes[:n_bytes])) != n_bytes:
+                        raise IOError(f'{fn}: short read')
+                raw = stage[:max((n_bytes + 1) // 2, 1)].to(d.device, non_blocking=False)
+                run.work(d.numel()).run(raw, out=d)
 
     def flac_failed_frames(self):
-        """Frames of the stores' FLAC files that failed their checks in `.device()` (one read of the device counters)."""
-        return sum(int(s.flac_failed.item()) for s in self.stores if getattr(s, 'flac_failed', None) is not None)
+        """Frames of the stores' FLAC files that failed their checks in `.device()` (one read of the device flags per store)."""
+        return sum(s.flac_failed.count() for s in self.stores if s.flac_failed is not None)
 
 
 def _randint(rng, low, high, size=None):

@@ -1,8 +1,6 @@
 """FLAC files: host side of `nafp_flac_*` (include/nafp.h).
 
-Opt-in: NAFP_INGEST_FLAC=1.  It includes everything NAFP_INGEST_CODECS=1 does (utils/codecs.py), and with it NAFP_INGEST_ANY=1 and
-NAFP_RESAMPLE=1; setting it together with any of them is the same as setting it alone.  Without it every loader refuses a `.flac`
-name as before.  A FLAC file is decoded on the device only (csrc/flac.hip, exact integer arithmetic): a pre-pass turns the WHOLE
+Opt-in: NAFP_INGEST_FLAC=1 (the layers: utils/resample.switches).  Without it every loader refuses a `.flac` name as before.  A FLAC file is decoded on the device only (csrc/flac.hip, exact integer arithmetic): a pre-pass turns the WHOLE
 FRAMES that cover a sample range into interleaved PCM of the file's own channel count and rate in a byte scratch tensor -- s16
 containers for up to 16 bits, s24 above, MSB-justified -- and the general ingest then reads that tensor as 16- or 24-bit PCM.  There
 is no CPU path, so whatever materialises samples on the host raises for such a file.
@@ -11,11 +9,11 @@ The frame index of a file (byte offset, byte length, first sample, block size pe
 over the file on the host (`scan`, nafp_flac_index_host).
 """
 import ctypes
-import os
 
 import numpy as np
 
 from ... import _lib
+from .resample import switches
 
 INFO_DTYPE = np.dtype(_lib.FLAC_INFO_DTYPE)
 INDEX_DTYPE = np.dtype(_lib.FLAC_INDEX_DTYPE)
@@ -29,7 +27,7 @@ REFUSALS = {1: 'Ogg-encapsulated FLAC is not taken (native FLAC streams are)',
 
 
 def enabled():
-    return os.environ.get('NAFP_INGEST_FLAC', '') == '1'
+    return switches().flac
 
 
 def container(bps):
@@ -152,9 +150,7 @@ class FailedFrames:
 def failed_count(source, dist=None):
     """Frames of a SegmentSource's / PcmStore's FLAC files that failed their checks in the launches so far: one read."""
     ff = getattr(source, 'flac_failed', None)
-    if ff is None:
-        return 0
-    return ff.count(dist) if isinstance(ff, FailedFrames) else int(ff.item())
+    return 0 if ff is None else ff.count(dist)
 
 
 class PrePass:

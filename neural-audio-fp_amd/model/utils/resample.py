@@ -4,6 +4,7 @@ Opt-in: NAFP_RESAMPLE=1.  Without it every loader raises on anything but FS-rate
 (model/utils/audio_utils.py:160-169).  The conversion itself exists on the device only (csrc/resample.hip, exact integer
 arithmetic): there is no CPU resampler here, so whatever materialises samples on the host raises for such a file.
 """
+import collections
 import ctypes
 import os
 
@@ -13,9 +14,23 @@ from ... import _lib
 
 PIECE_DTYPE = np.dtype(_lib.RESAMPLE_PIECE_DTYPE)
 
+Switches = collections.namedtuple('Switches', 'resample ingest codecs flac resample_itself')
+
+
+def switches():
+    """The opt-in layers of audio ingest as the environment sets them, the one place that reads it.  Each layer includes the
+    ones before it, so setting one together with an earlier one is the same as setting it alone:
+      resample  NAFP_RESAMPLE=1       16-bit PCM in mono or stereo at a higher rate; its own kernel (nafp_resample_*, this module)
+      ingest    NAFP_INGEST_ANY=1     any PCM / float format, 1 to 8 channels, rates in either direction (utils/ingest.py)
+      codecs    NAFP_INGEST_CODECS=1  A-law, mu-law, IMA and MS ADPCM too, decoded by a pre-pass of whole blocks (utils/codecs.py)
+      flac      NAFP_INGEST_FLAC=1    `.flac` names too, decoded by a pre-pass of whole frames (utils/flac.py)
+    `resample_itself`: NAFP_RESAMPLE=1 is set, whatever else is."""
+    on = [os.environ.get(k, '') == '1' for k in ('NAFP_RESAMPLE', 'NAFP_INGEST_ANY', 'NAFP_INGEST_CODECS', 'NAFP_INGEST_FLAC')]
+    return Switches(any(on), any(on[1:]), any(on[2:]), on[3], on[0])
+
 
 def enabled():
-    return os.environ.get('NAFP_RESAMPLE', '') == '1'
+    return switches().resample_itself
 
 
 def geometry(fs_in, fs_out):
@@ -110,25 +125,17 @@ def plan_for(fs_in, fs_out, device=None):
     return _PLANS[key]
 
 
-class ChunkPieces:
-    """The resampling work of one launch: raw arena -> `out_total` int16 at the model rate; `by_rate` maps fs_in to the host
-    piece array of that rate (files at the model rate in mono ride along through the identity plan)."""
-
-    def __init__(self, fs_out, by_rate, out_total):
-        self.fs_out, self.by_rate, self.out_total = fs_out, by_rate, int(out_total)
-
-    def run(self, raw_dev):
-        import torch
-        out = torch.empty((max(self.out_total, 1),), dtype=torch.int16, device=raw_dev.device)
-        for fs_in, pieces in self.by_rate.items():
-            plan_for(fs_in, self.fs_out, raw_dev.device).run(raw_dev, pieces, out)
-        return out
+def as_raw(t):
+    """The uploaded arena as this kernel takes it: int16, as the loaders' buffers are."""
+    return t
 
 
-def rates_summary(source):
-    """{'files': n, 'resampled': k, 'rates': {'44100x2': count, ...}} of a SegmentSource / PcmStore."""
+def rates_summary(source, formats=False):
+    """{'files': n, 'resampled': k, 'rates': {'44100x2': count, ...}} of a SegmentSource / PcmStore; 'resampled' counts the files
+    that are converted on the device.  formats=True (utils/ingest.rates_summary): rate x channels x sample format per file class,
+    e.g. '48000x2xs24'."""
     rates = {}
-    for r, c in zip(source.rate, source.channels):
-        key = f'{r}x{c}'
+    for row in zip(source.rate, source.channels, *([source.format] if formats else [])):
+        key = 'x'.join(str(v) for v in row)
         rates[key] = rates.get(key, 0) + 1
     return {'files': len(source.rate), 'resampled': int(sum(bool(x) for x in source.resampled)), 'rates': rates}

@@ -52,7 +52,7 @@ def pieces_for(mod, fs_in, fs_out, frame_bytes, unit, extra):
 
 
 def codec_pieces(ig, cd, codec, fs_in, fs_out, ch, align):
-    """The launch of a codec tree as SegmentSource._ingest_chunk cuts it: per 30-s file the whole blocks that cover the frames its
+    """The launch of a codec tree as SegmentSource.iter_windows cuts it (ingest.LaunchPlan): per 30-s file the whole blocks that cover the frames its
     outputs read, decoded into a scratch arena that the file's ingest piece (16-bit PCM) indexes.
     -> (codec piece array, ingest piece array, raw bytes, scratch int16, outputs)."""
     spb = cd.samples_per_block(codec, ch, align)
@@ -71,7 +71,7 @@ def codec_pieces(ig, cd, codec, fs_in, fs_out, ch, align):
 
 
 def flac_launch(ig, fl, index, fs_in, fs_out, file_bytes):
-    """The launch of a FLAC tree as SegmentSource._ingest_chunk cuts it: per 30-s file the whole frames that cover the samples its
+    """The launch of a FLAC tree as SegmentSource.iter_windows cuts it (ingest.LaunchPlan): per 30-s file the whole frames that cover the samples its
     outputs read.  -> (frame records, ingest piece array, raw bytes, scratch bytes, outputs, [(raw offset, file byte range)])."""
     total_out = (SEGMENTS - 1) * (fs_out // 2) + fs_out
     n_in = int(index.start[-1])

@@ -17,18 +17,22 @@
 //                              smaller list id)
 //   ivf_flat_lists_kernel      the lists' rows copied contiguously, each list padded to whole 64-row tiles (+inf half norms)
 //   ivf_flat_scan_kernel       (search.hip) the exact search's fp32-MFMA body over one list for the queries probing it
-//   ivf_pq_scan_kernel<DSUB,K> per (query, list) pair: the fp32 ADC table (64 x 256, 64 KB of LDS), then the list's 64-byte
-//                              codes, 64 LDS lookups per row, summed in sub-space order; register top-K per lane, then a
-//                              workgroup-wide K-way selection
-//   ivf_pq_scan_f16_kernel<DSUB,K>  the same with the table rounded once to binary16 (NAFP_IVF_LUT_F16, the reference's
-//                              useFloat16 lookup tables): 32 KB of table, entries widened to fp32 and summed in fp32 in
-//                              sub-space order.  The selection does not go through the table area: each wave reduces its 64
-//                              lane lists in registers (K rounds of a wave arg-max of the heads, the winner shifts its list),
-//                              then the 4 x K wave results are ranked by counting -- 34 KB of LDS in all, four workgroups per CU
+//   the three IVF-PQ scans     one workgroup per (query, list) pair and part of the list.  What they share is written once:
+//                              ivf_scan_prologue (residual to the coarse centroid; the 64 x 256 ADC table in LDS through
+//                              ivf_adc_entry, fp32 or rounded once to binary16; the part's rows), IvfRowCodes::load (a row's 64
+//                              code bytes, loaded one row ahead) and ivf_row_key (64 LDS lookups, summed in fp32 in sub-space
+//                              order).  Each kernel keeps its own loop header, selection and LDS carve-up
+//                              (ivf_pq_scan*_lds_bytes next to it):
+//   ivf_pq_scan_kernel<DSUB,K>      fp32 table.  K sorted entries per lane in registers, then a workgroup-wide K-way arg-max
+//                              over the lane lists parked in the table area
+//   ivf_pq_scan_f16_kernel<DSUB,K>  binary16 table (NAFP_IVF_LUT_F16, the reference's useFloat16 lookup tables).  K sorted
+//                              entries per lane, each wave reduces its 64 lane lists in registers (K rounds of a wave
+//                              arg-max of the heads, the winner shifts its list), the 4 x K wave results ranked by counting
+//   ivf_pq_scan_wide_kernel<DSUB,LUT>  IVFPQ-RR's first stage, either table, K <= 128 at run time.  A filter per wave
+//                              (threshold + LDS candidate buffer, pruned to K by bisection when full), the 4 x (<= K) wave
+//                              results ranked by counting
 //   ivf_pq_adc_tables_kernel<DSUB,LUT>  the tables themselves for given (query, list) pairs (ivf_adc_entry, as the scans)
 //   ivf_merge_kernel           per query: the probes' partial lists -> k results (distance asc, id asc), -1 / +inf padding
-//   ivf_pq_scan_wide_kernel<DSUB,LUT>  IVFPQ-RR's first stage: either scan for K <= 128 results (run time); the selection is a
-//                              filter per wave (threshold + LDS candidate buffer, pruned to K by bisection when full)
 //   ivf_pq_residual2_kernel    x - decode(codes): what the refine quantizer is trained on and encodes
 //   ivf_refine_encode_kernel<DR>  per row the nearest of 16 codewords in each of 4 sub-spaces of DR = 16 / 32 / 64 dimensions
 //   ivf_pqr_rerank_kernel<DSUB>  per query: the candidates' list, PQ code and refine code gathered, the fp32 distance to the
@@ -38,6 +42,7 @@
 #include <hip/hip_fp16.h>
 
 #include <algorithm>
+#include <type_traits>
 
 namespace nafp {
 
@@ -296,8 +301,21 @@ __global__ void ivf_qblock_prefix_kernel(const int* __restrict__ pair_off, int n
     qblk_off[nlist] = run;
 }
 
+// ---- the IVF-PQ scans' shared pieces --------------------------------------------------------------------------------------
+// What an IVF-PQ distance IS, once: the residual, the table entry and its rounding point, the split of a list into parts, the
+// load of a row's codes and the 64-lookup sum.  The three scan kernels below differ in their selection only.
+constexpr int PQ_NT = PQ_M * PQ_KS;         // entries of an ADC table
+template <int LUT> using ivf_lut_t = std::conditional_t<LUT == 0, float, __half>;     // LUT 0: fp32 entries, LUT 1: binary16
+
+// rr[0 .. D) = query q - coarse centroid l (the caller's barrier follows)
+template <int DSUB>
+__device__ __forceinline__ void ivf_residual_fill(float* rr, const float* Q, int q, const float* coarse, int l) {
+    constexpr int D = PQ_M * DSUB;
+    for (int dd = threadIdx.x; dd < D; dd += 256) rr[dd] = Q[(int64_t)q * D + dd] - coarse[(int64_t)l * D + dd];
+}
+
 // ADC table entry e = m * 256 + c of the residual rr (fp32, D entries): sum_u (rr[m * DSUB + u] - P[m][c][u])^2, u ascending.
-// The one place the table is computed: both scans and the export call it.
+// The one place an entry is computed: the scans' table fill (ivf_scan_prologue) and the export call it.
 template <int DSUB>
 __device__ __forceinline__ float ivf_adc_entry(const float* rr, const float* __restrict__ pq, int e) {
     const int m = e >> 8;
@@ -306,6 +324,60 @@ __device__ __forceinline__ float ivf_adc_entry(const float* rr, const float* __r
 #pragma unroll
     for (int u = 0; u < DSUB; ++u) { const float t = rr[m * DSUB + u] - c[u]; s += t * t; }
     return s;
+}
+
+// Workgroup (blockIdx.x, blockIdx.y) = (pair, part): the pair's residual into rr, its ADC table into `table` -- every entry in
+// fp32, for LUT 1 rounded once to binary16 (nearest even, subnormals kept: v_cvt_f16_f32 follows the f16 denormal mode, which is
+// on) -- and the part's rows: [r0, r1) of the list that starts at row o0 of the sorted codes.  rr is dead after the second barrier.
+struct IvfScanTask { int o0, r0, r1; };
+template <int DSUB, int LUT>
+__device__ __forceinline__ IvfScanTask ivf_scan_prologue(ivf_lut_t<LUT>* table, float* rr, const float* Q, const int* qmap,
+                                                         const int* plist, const float* coarse, const float* pq, const int* off,
+                                                         int parts) {
+    const int tid = threadIdx.x;
+    const int64_t pos = blockIdx.x;
+    const int part = blockIdx.y;
+    const int q = qmap[pos], l = plist[pos];
+    ivf_residual_fill<DSUB>(rr, Q, q, coarse, l);
+    __syncthreads();
+    for (int e = tid; e < PQ_NT; e += 256) {
+        const float ent = ivf_adc_entry<DSUB>(rr, pq, e);
+        if constexpr (LUT == 0) table[e] = ent;
+        else                    table[e] = __float2half_rn(ent);
+    }
+    __syncthreads();
+    const int o0 = off[l];
+    const int len = off[l + 1] - o0;
+    const int per = (len + parts - 1) / parts;
+    const int r0 = std::min(len, part * per);
+    return {o0, r0, std::min(len, r0 + per)};
+}
+
+// a row's 64 code bytes.  The scans load the next row's before this row's lookups (they come from L2 / MALL; 8 - 16 waves per
+// CU hide little): `next.load(..)` ahead of the loop, then per trip `cur = next`, the next load, the lookups of cur.
+struct IvfRowCodes {
+    uint4 w0 = make_uint4(0u, 0u, 0u, 0u), w1 = w0, w2 = w0, w3 = w0;
+    __device__ __forceinline__ void load(const unsigned char* codes, int row) {
+        const uint4* cp = (const uint4*)(codes + (int64_t)row * PQ_M);
+        w0 = cp[0]; w1 = cp[1]; w2 = cp[2]; w3 = cp[3];
+    }
+    __device__ __forceinline__ unsigned code(int m) const {      // sub-space m's code (m: a constant of an unrolled loop)
+        const unsigned w[16] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w, w3.x, w3.y, w3.z, w3.w};
+        return (w[m >> 2] >> (8 * (m & 3))) & 255u;
+    }
+};
+
+// the key of a row, -distance: the 64 entries its codes pick, m ascending, added in fp32 (binary16 entries widened first).
+// The one place a row's distance is computed.
+template <int LUT>
+__device__ __forceinline__ float ivf_row_key(const ivf_lut_t<LUT>* table, const IvfRowCodes& c) {
+    float s = 0.f;
+#pragma unroll
+    for (int m = 0; m < PQ_M; ++m) {
+        if constexpr (LUT == 0) s += table[m * PQ_KS + c.code(m)];
+        else                    s += __half2float(table[m * PQ_KS + c.code(m)]);
+    }
+    return -s;
 }
 
 // sorted insert into a lane's descending (sc, id) list; the caller has checked key > sc[K - 1].  Rows ascend within the
@@ -321,52 +393,34 @@ __device__ __forceinline__ void ivf_topk_insert(float (&sc)[K], int (&id)[K], fl
     if (key > sc[0]) { sc[0] = key; id[0] = nid; }
 }
 
-// one workgroup per (pair, part): ADC table of the pair in LDS, then rows [r0, r1) of the list's part
+// The fp32 narrow scan.  Selection: K sorted entries per lane in registers, then the 256 lane lists go to the table area (the
+// table is done) and K rounds of a workgroup-wide arg-max of the heads pick the results.
+// LDS: 65 536 B table + 1 024 B residual + 32 B wave bests = 66 592 B: two workgroups per CU.
+constexpr int ivf_pq_scan_lds_bytes() { return PQ_NT * 4 + 256 * 4 + 4 * 8; }
 template <int DSUB, int K>
 __global__ __launch_bounds__(256) void ivf_pq_scan_kernel(const float* __restrict__ Q, const int* __restrict__ qmap,
                                                           const int* __restrict__ plist, const float* __restrict__ coarse,
                                                           const float* __restrict__ pq, const unsigned char* __restrict__ codes,
                                                           const int* __restrict__ off, const int* __restrict__ ids, int parts,
                                                           float* __restrict__ pk, int* __restrict__ pi) {
-    constexpr int D = PQ_M * DSUB, NT = PQ_M * PQ_KS;
-    extern __shared__ __attribute__((aligned(16))) float lut[];   // [NT] table, then [D] residual, [4] x u64 wave bests
-    float* rr = lut + NT;
+    extern __shared__ __attribute__((aligned(16))) float lut[];   // [PQ_NT] table, then [256] residual, [4] x u64 wave bests
+    float* rr = lut + PQ_NT;
     unsigned long long* wbest = (unsigned long long*)(rr + 256);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t pos = blockIdx.x;
     const int part = blockIdx.y;
-    const int q = qmap[pos], l = plist[pos];
-    for (int dd = tid; dd < D; dd += 256) rr[dd] = Q[(int64_t)q * D + dd] - coarse[(int64_t)l * D + dd];
-    __syncthreads();
-    for (int e = tid; e < NT; e += 256) lut[e] = ivf_adc_entry<DSUB>(rr, pq, e);
-    __syncthreads();
-    const int o0 = off[l];
-    const int len = off[l + 1] - o0;
-    const int per = (len + parts - 1) / parts;
-    const int r0 = std::min(len, part * per), r1 = std::min(len, r0 + per);
+    const IvfScanTask t = ivf_scan_prologue<DSUB, 0>(lut, rr, Q, qmap, plist, coarse, pq, off, parts);
     float sc[K]; int id[K];
 #pragma unroll
     for (int j = 0; j < K; ++j) { sc[j] = -INFINITY; id[j] = -1; }
-    // the next row's codes are loaded before this row's lookups (they come from L2 / MALL; 8 waves per CU hide little)
-    uint4 n0 = make_uint4(0u, 0u, 0u, 0u), n1 = n0, n2 = n0, n3 = n0;
-    if (r0 + tid < r1) {
-        const uint4* cp = (const uint4*)(codes + (int64_t)(o0 + r0 + tid) * PQ_M);
-        n0 = cp[0]; n1 = cp[1]; n2 = cp[2]; n3 = cp[3];
+    IvfRowCodes next;
+    if (t.r0 + tid < t.r1) next.load(codes, t.o0 + t.r0 + tid);
+    for (int r = t.r0 + tid; r < t.r1; r += 256) {                // a per-lane trip count
+        const IvfRowCodes cur = next;
+        if (r + 256 < t.r1) next.load(codes, t.o0 + r + 256);
+        const float key = ivf_row_key<0>(lut, cur);
+        if (key > sc[K - 1]) ivf_topk_insert<K>(sc, id, key, ids[t.o0 + r]);
     }
-    for (int r = r0 + tid; r < r1; r += 256) {
-        const uint4 w0 = n0, w1 = n1, w2 = n2, w3 = n3;
-        if (r + 256 < r1) {
-            const uint4* cp = (const uint4*)(codes + (int64_t)(o0 + r + 256) * PQ_M);
-            n0 = cp[0]; n1 = cp[1]; n2 = cp[2]; n3 = cp[3];
-        }
-        const unsigned w[16] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w, w3.x, w3.y, w3.z, w3.w};
-        float s = 0.f;
-#pragma unroll
-        for (int m = 0; m < PQ_M; ++m) s += lut[m * PQ_KS + ((w[m >> 2] >> (8 * (m & 3))) & 255u)];
-        const float key = -s;
-        if (key > sc[K - 1]) ivf_topk_insert<K>(sc, id, key, ids[o0 + r]);
-    }
-    // workgroup top-K: the 256 sorted lane lists in LDS (the table is done), K rounds of a workgroup-wide arg-max of the heads
     __syncthreads();
     unsigned long long* cl = (unsigned long long*)lut;
 #pragma unroll
@@ -392,58 +446,40 @@ __global__ __launch_bounds__(256) void ivf_pq_scan_kernel(const float* __restric
     }
 }
 
-// The same scan with the table in binary16 (NAFP_IVF_LUT_F16).  Entry: ivf_adc_entry in fp32, rounded once (nearest even,
-// subnormals kept: v_cvt_f16_f32 follows the f16 denormal mode, which is on); a row's distance: the 64 entries widened to fp32
-// and added in fp32, m ascending.  Table layout: plain [m][c] halves, i.e. codes c and c ^ 1 share a dword and dword c / 2 of a
-// sub-table sits on bank (c / 2) % 32.  A lookup instruction reads ONE sub-table for all lanes (same m, the lanes' own
-// codes), and the codes of different rows are unrelated, so any placement of the 256 entries on 128 dwords puts 4 dwords on
-// each bank and meets the same conflicts; this one needs no address arithmetic beyond c * 2 (m * 512 is the instruction's
-// offset) and its table fill is conflict-free.  Lanes with equal or paired codes read one dword (broadcast).
-// LDS: 32 KB table + 1 KB residual + 4 * K * 8 B wave results = 34 432 / 34 816 B (K = 20 / 32): four workgroups per CU
+// The fp16 narrow scan (NAFP_IVF_LUT_F16): the same rows and sums over the table in binary16.  Table layout: plain [m][c]
+// halves, i.e. codes c and c ^ 1 share a dword and dword c / 2 of a sub-table sits on bank (c / 2) % 32.  A lookup instruction
+// reads ONE sub-table for all lanes (same m, the lanes' own codes), and the codes of different rows are unrelated, so any
+// placement of the 256 entries on 128 dwords puts 4 dwords on each bank and meets the same conflicts; this one needs no address
+// arithmetic beyond c * 2 (m * 512 is the instruction's offset) and its table fill is conflict-free.  Lanes with equal or
+// paired codes read one dword (broadcast).  Selection: K sorted entries per lane as above, but not through the table area: each
+// wave reduces its 64 lane lists in registers, then the 4 x K wave results are ranked by counting.
+// LDS: 32 768 B table + 1 024 B residual + 4 * K * 8 B wave results = 34 432 / 34 816 B (K = 20 / 32): four workgroups per CU
 // (16 waves, 4 per SIMD); the registers allow that (83 / 116 VGPRs, build/ivf.resources.txt).
+constexpr int ivf_pq_scan_f16_lds_bytes(int K) { return PQ_NT * 2 + 256 * 4 + 4 * K * 8; }
 template <int DSUB, int K>
 __global__ __launch_bounds__(256) void ivf_pq_scan_f16_kernel(const float* __restrict__ Q, const int* __restrict__ qmap,
                                                               const int* __restrict__ plist, const float* __restrict__ coarse,
                                                               const float* __restrict__ pq, const unsigned char* __restrict__ codes,
                                                               const int* __restrict__ off, const int* __restrict__ ids, int parts,
                                                               float* __restrict__ pk, int* __restrict__ pi) {
-    constexpr int D = PQ_M * DSUB, NT = PQ_M * PQ_KS;
-    extern __shared__ __attribute__((aligned(16))) float lds_f16[];    // [NT] halves, then [256] residual, [4 * K] x u64 wave results
+    extern __shared__ __attribute__((aligned(16))) float lds_f16[];    // [PQ_NT] halves, then [256] residual, [4 * K] x u64 wave results
     __half* lut = (__half*)lds_f16;
-    float* rr = lds_f16 + NT / 2;
+    float* rr = lds_f16 + PQ_NT / 2;
     unsigned long long* wres = (unsigned long long*)(rr + 256);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t pos = blockIdx.x;
     const int part = blockIdx.y;
-    const int q = qmap[pos], l = plist[pos];
-    for (int dd = tid; dd < D; dd += 256) rr[dd] = Q[(int64_t)q * D + dd] - coarse[(int64_t)l * D + dd];
-    __syncthreads();
-    for (int e = tid; e < NT; e += 256) lut[e] = __float2half_rn(ivf_adc_entry<DSUB>(rr, pq, e));
-    __syncthreads();
-    const int o0 = off[l];
-    const int len = off[l + 1] - o0;
-    const int per = (len + parts - 1) / parts;
-    const int r0 = std::min(len, part * per), r1 = std::min(len, r0 + per);
+    const IvfScanTask t = ivf_scan_prologue<DSUB, 1>(lut, rr, Q, qmap, plist, coarse, pq, off, parts);
     float sc[K]; int id[K];
 #pragma unroll
     for (int j = 0; j < K; ++j) { sc[j] = -INFINITY; id[j] = -1; }
-    uint4 n0 = make_uint4(0u, 0u, 0u, 0u), n1 = n0, n2 = n0, n3 = n0;     // the next row's codes, loaded a row ahead
-    if (r0 + tid < r1) {
-        const uint4* cp = (const uint4*)(codes + (int64_t)(o0 + r0 + tid) * PQ_M);
-        n0 = cp[0]; n1 = cp[1]; n2 = cp[2]; n3 = cp[3];
-    }
-    for (int r = r0 + tid; r < r1; r += 256) {
-        const uint4 w0 = n0, w1 = n1, w2 = n2, w3 = n3;
-        if (r + 256 < r1) {
-            const uint4* cp = (const uint4*)(codes + (int64_t)(o0 + r + 256) * PQ_M);
-            n0 = cp[0]; n1 = cp[1]; n2 = cp[2]; n3 = cp[3];
-        }
-        const unsigned w[16] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w, w3.x, w3.y, w3.z, w3.w};
-        float s = 0.f;
-#pragma unroll
-        for (int m = 0; m < PQ_M; ++m) s += __half2float(lut[m * PQ_KS + ((w[m >> 2] >> (8 * (m & 3))) & 255u)]);
-        const float key = -s;
-        if (key > sc[K - 1]) ivf_topk_insert<K>(sc, id, key, ids[o0 + r]);
+    IvfRowCodes next;
+    if (t.r0 + tid < t.r1) next.load(codes, t.o0 + t.r0 + tid);
+    for (int r = t.r0 + tid; r < t.r1; r += 256) {                // a per-lane trip count
+        const IvfRowCodes cur = next;
+        if (r + 256 < t.r1) next.load(codes, t.o0 + r + 256);
+        const float key = ivf_row_key<1>(lut, cur);
+        if (key > sc[K - 1]) ivf_topk_insert<K>(sc, id, key, ids[t.o0 + r]);
     }
     // wave top-K in registers: K rounds of a wave-wide arg-max of the lanes' heads; the winning lane drops its head (a shift
     // by one with static indices: no scratch).  Packed values are distinct (ids are), 0 = nothing left.
@@ -479,19 +515,17 @@ template <int DSUB, int LUT>
 __global__ __launch_bounds__(256) void ivf_pq_adc_tables_kernel(const float* __restrict__ Q, int64_t n_query, const int* __restrict__ pair_query,
                                                                 const int* __restrict__ pair_list, const float* __restrict__ coarse, int nlist,
                                                                 const float* __restrict__ pq, void* __restrict__ out) {
-    constexpr int D = PQ_M * DSUB, NT = PQ_M * PQ_KS;
     __shared__ float rr[256];
     const int tid = threadIdx.x;
     const int64_t p = blockIdx.x;
     const int q = pair_query[p], l = pair_list[p];
     const bool ok = q >= 0 && q < n_query && l >= 0 && l < nlist;
-    if (ok)
-        for (int dd = tid; dd < D; dd += 256) rr[dd] = Q[(int64_t)q * D + dd] - coarse[(int64_t)l * D + dd];
+    if (ok) ivf_residual_fill<DSUB>(rr, Q, q, coarse, l);
     __syncthreads();
-    for (int e = tid; e < NT; e += 256) {
+    for (int e = tid; e < PQ_NT; e += 256) {
         const float s = ok ? ivf_adc_entry<DSUB>(rr, pq, e) : NAN;
-        if (LUT == 0) ((float*)out)[p * NT + e] = s;
-        else          ((__half*)out)[p * NT + e] = __float2half_rn(s);
+        if (LUT == 0) ((float*)out)[p * PQ_NT + e] = s;
+        else          ((__half*)out)[p * PQ_NT + e] = __float2half_rn(s);
     }
 }
 
@@ -505,8 +539,9 @@ __global__ __launch_bounds__(256) void ivf_pq_adc_tables_kernel(const float* __r
 // Packed values are distinct (ids are), so after a prune exactly K remain and the threshold is exact.  What a wave holds at the end
 // is the K best of ITS rows whatever the order of appends and the timing of prunes; the 4 x (<= K) wave results are then ranked by
 // counting, as the fp16 scan does, and the K best go out sorted.  Results therefore do not depend on scheduling or batching.
+// The table fill, the rows and the 64-lookup sum are the narrow scans' (the shared pieces above).
 // LDS: the table, then the four buffers (they overlay the residual, which is dead once the table is built) and 4 counts:
-// fp32 65 536 + 7 680 + 16 = 73 232 B (two workgroups per CU), fp16 32 768 + 7 680 + 16 = 40 464 B (four).
+// table + 7 680 + 16, i.e. fp32 65 536 + 7 680 + 16 = 73 232 B (two workgroups per CU), fp16 32 768 + 7 680 + 16 = 40 464 B (four).
 constexpr int WIDE_CAP = 240;               // candidates per wave buffer (>= 128 + 64: a prune always makes room for one append)
 constexpr int WIDE_REGS = (WIDE_CAP + 63) / 64;
 constexpr int WIDE_KMAX = 128;
@@ -543,61 +578,36 @@ __device__ __forceinline__ unsigned long long ivf_wide_prune(unsigned long long*
     return t;
 }
 
+constexpr int ivf_pq_scan_wide_lds_bytes(int lut) { return PQ_NT * (lut == 0 ? 4 : 2) + 4 * WIDE_CAP * 8 + 16; }
 template <int DSUB, int LUT>
 __global__ __launch_bounds__(256) void ivf_pq_scan_wide_kernel(const float* __restrict__ Q, const int* __restrict__ qmap,
                                                                const int* __restrict__ plist, const float* __restrict__ coarse,
                                                                const float* __restrict__ pq, const unsigned char* __restrict__ codes,
                                                                const int* __restrict__ off, const int* __restrict__ ids, int parts, int K,
                                                                float* __restrict__ pk, int* __restrict__ pi) {
-    constexpr int D = PQ_M * DSUB, NT = PQ_M * PQ_KS, TABLE_FLOATS = LUT == 0 ? NT : NT / 2;
+    constexpr int TABLE_FLOATS = LUT == 0 ? PQ_NT : PQ_NT / 2;
     extern __shared__ __attribute__((aligned(16))) float lds_wide[];  // table, then [4][WIDE_CAP] u64 (over the residual), [4] counts
-    float* lutf = lds_wide;
-    __half* luth = (__half*)lds_wide;
-    float* rr = lds_wide + TABLE_FLOATS;
+    ivf_lut_t<LUT>* lut = (ivf_lut_t<LUT>*)lds_wide;
     unsigned long long* cbuf = (unsigned long long*)(lds_wide + TABLE_FLOATS);
     int* wcnt = (int*)(cbuf + 4 * WIDE_CAP);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t pos = blockIdx.x;
     const int part = blockIdx.y;
-    const int q = qmap[pos], l = plist[pos];
-    for (int dd = tid; dd < D; dd += 256) rr[dd] = Q[(int64_t)q * D + dd] - coarse[(int64_t)l * D + dd];
-    __syncthreads();
-    for (int e = tid; e < NT; e += 256) {
-        const float ent = ivf_adc_entry<DSUB>(rr, pq, e);
-        if (LUT == 0) lutf[e] = ent;
-        else          luth[e] = __float2half_rn(ent);
-    }
-    __syncthreads();                                              // the residual is dead from here: its place is the buffers'
-    const int o0 = off[l];
-    const int len = off[l + 1] - o0;
-    const int per = (len + parts - 1) / parts;
-    const int r0 = std::min(len, part * per), r1 = std::min(len, r0 + per);
+    // the residual is dead after the prologue: its place is the buffers'
+    const IvfScanTask t = ivf_scan_prologue<DSUB, LUT>(lut, lds_wide + TABLE_FLOATS, Q, qmap, plist, coarse, pq, off, parts);
+    const int o0 = t.o0, r1 = t.r1;
     unsigned long long* buf = cbuf + wave * WIDE_CAP;
     const unsigned long long below = (1ull << lane) - 1ull;
     unsigned long long thr = 0ull;                                // a candidate must beat it (0: nothing yet)
     float thr_key = -INFINITY;
     int cnt = 0;
-    uint4 n0 = make_uint4(0u, 0u, 0u, 0u), n1 = n0, n2 = n0, n3 = n0;     // the next row's codes, loaded a row ahead
-    if (r0 + tid < r1) {
-        const uint4* cp = (const uint4*)(codes + (int64_t)(o0 + r0 + tid) * PQ_M);
-        n0 = cp[0]; n1 = cp[1]; n2 = cp[2]; n3 = cp[3];
-    }
-    for (int rb = r0; rb < r1; rb += 256) {                       // a uniform trip count: the wave's count stays wave-uniform
+    IvfRowCodes next;
+    if (t.r0 + tid < r1) next.load(codes, o0 + t.r0 + tid);
+    for (int rb = t.r0; rb < r1; rb += 256) {                     // a uniform trip count: the wave's count stays wave-uniform
         const int r = rb + tid;
-        const uint4 w0 = n0, w1 = n1, w2 = n2, w3 = n3;
-        if (r + 256 < r1) {
-            const uint4* cp = (const uint4*)(codes + (int64_t)(o0 + r + 256) * PQ_M);
-            n0 = cp[0]; n1 = cp[1]; n2 = cp[2]; n3 = cp[3];
-        }
-        const unsigned w[16] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w, w3.x, w3.y, w3.z, w3.w};
-        float s = 0.f;
-#pragma unroll
-        for (int m = 0; m < PQ_M; ++m) {
-            const unsigned c = (w[m >> 2] >> (8 * (m & 3))) & 255u;
-            if (LUT == 0) s += lutf[m * PQ_KS + c];
-            else          s += __half2float(luth[m * PQ_KS + c]);
-        }
-        const float key = -s;
+        const IvfRowCodes cur = next;
+        if (r + 256 < r1) next.load(codes, o0 + r + 256);
+        const float key = ivf_row_key<LUT>(lut, cur);
         unsigned long long p = 0ull;
         if (r < r1 && key >= thr_key) p = ivf_pack(key, ids[o0 + r]);     // equal distances: the ids decide, below
         const bool take = p > thr;
@@ -720,14 +730,13 @@ __global__ __launch_bounds__(WIDE_KMAX) void ivf_pqr_rerank_kernel(const float* 
     const int id = tid < k1 ? cand[q * k1 + tid] : -1;
     if (id >= 0 && id < n_rows) {
         const float* cr = coarse + (int64_t)assign[id] * D;
-        const uint4* cp = (const uint4*)(codes + (int64_t)id * PQ_M);
-        const uint4 w0 = cp[0], w1 = cp[1], w2 = cp[2], w3 = cp[3];
-        const unsigned w[16] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w, w3.x, w3.y, w3.z, w3.w};
+        IvfRowCodes row;
+        row.load(codes, id);
         const unsigned rc = (unsigned)rcodes[(int64_t)id * 2] | ((unsigned)rcodes[(int64_t)id * 2 + 1] << 8);
         float s = 0.f;
 #pragma unroll
         for (int m = 0; m < PQ_M; ++m) {
-            const float* pc = pq + ((int64_t)m * PQ_KS + ((w[m >> 2] >> (8 * (m & 3))) & 255u)) * DSUB;
+            const float* pc = pq + ((int64_t)m * PQ_KS + row.code(m)) * DSUB;
             const int mr = m >> 4;                                // DR = 16 * DSUB: 16 PQ sub-spaces per refine sub-space
             const float* rp = rf + (mr * RF_KS + ((rc >> (4 * mr)) & 15u)) * DR + (m & 15) * DSUB;
 #pragma unroll
@@ -800,6 +809,20 @@ __global__ __launch_bounds__(64) void ivf_merge_kernel(const float* __restrict__
 }
 
 static bool ivf_dim_ok(int dim) { return dim == 64 || dim == 128 || dim == 256; }
+
+// The one dispatch of a run-time size onto the compiled ones: f(std::integral_constant<int, DSUB>) for dsub = dim / 64 in
+// 1, 2, 4 (the caller has checked ivf_dim_ok), and a choice between two (K = 20 / 32, lut = 0 / 1) to nest inside it.
+template <int V> using ivf_const = std::integral_constant<int, V>;
+template <typename F>
+static void ivf_with_dsub(int dim, F&& f) {
+    switch (dim / PQ_M) {
+        case 1: f(ivf_const<1>{}); break;
+        case 2: f(ivf_const<2>{}); break;
+        default: f(ivf_const<4>{}); break;
+    }
+}
+template <int A, int B, typename F>
+static void ivf_with_either(bool first, F&& f) { if (first) f(ivf_const<A>{}); else f(ivf_const<B>{}); }
 static int ivf_nbits(int nb) { int b = 0; while ((1 << b) < nb) ++b; return b; }
 static int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
 
@@ -879,11 +902,8 @@ extern "C" int nafp_ivf_pq_encode(const float* x, int64_t n, int dim, const int3
     if (!ivf_dim_ok(dim) || M != PQ_M || n >= ((int64_t)1 << 31)) return NAFP_ERR_UNSUPPORTED;
     if (n == 0) return NAFP_OK;
     hipStream_t st = (hipStream_t)stream;
-    const int dsub = dim / M;
-    const dim3 grid((unsigned)((n + 255) / 256), (unsigned)dsub);          // 64 / dsub sub-spaces per workgroup
-    if (dsub == 1)      ivf_pq_encode_kernel<1><<<grid, 256, 0, st>>>(x, n, assign, coarse, pq_centroids, codes);
-    else if (dsub == 2) ivf_pq_encode_kernel<2><<<grid, 256, 0, st>>>(x, n, assign, coarse, pq_centroids, codes);
-    else                ivf_pq_encode_kernel<4><<<grid, 256, 0, st>>>(x, n, assign, coarse, pq_centroids, codes);
+    const dim3 grid((unsigned)((n + 255) / 256), (unsigned)(dim / M));     // 64 / dsub sub-spaces per workgroup
+    ivf_with_dsub(dim, [&](auto ds) { ivf_pq_encode_kernel<ds()><<<grid, 256, 0, st>>>(x, n, assign, coarse, pq_centroids, codes); });
     NAFP_LAUNCH_CHECK();
     return NAFP_OK;
 }
@@ -1013,43 +1033,52 @@ extern "C" int nafp_ivf_flat_search(const float* query, int64_t n_query, const f
 
 static bool ivf_lut_ok(int lut) { return lut == NAFP_IVF_LUT_F32 || lut == NAFP_IVF_LUT_F16; }
 
-extern "C" int nafp_ivf_pq_search_ex(const float* query, int64_t n_query, const float* centroids, int nlist, int dim, int nprobe,
-                                     const float* pq_centroids, int M, const uint8_t* codes_sorted, const int32_t* offsets,
-                                     const int32_t* ids, int k, float* out_dist, int32_t* out_ids, int lut, void* workspace,
-                                     int64_t workspace_bytes, void* stream) {
+// The IVF-PQ search, k <= 32 through the two narrow scans or (wide) k <= 128 through the wide one: checks, layout, probe and
+// pair grouping, the scan of the (pair, part) grid into the partial lists, the merge.
+static int ivf_pq_search_run(bool wide, const float* query, int64_t n_query, const float* centroids, int nlist, int dim, int nprobe,
+                             const float* pq_centroids, int M, const uint8_t* codes_sorted, const int32_t* offsets, const int32_t* ids,
+                             int k, float* out_dist, int32_t* out_ids, int lut, void* workspace, int64_t workspace_bytes, void* stream) {
     if (!query || !centroids || !pq_centroids || !codes_sorted || !offsets || !ids || !out_dist || !out_ids || !workspace ||
         n_query < 0 || nlist <= 0 || nprobe <= 0 || k <= 0)
         return NAFP_ERR_INVALID_ARG;
     IvfSearchLayout L;
-    if (!ivf_dim_ok(dim) || M != PQ_M || !ivf_lut_ok(lut) || !ivf_search_layout(n_query, nlist, nprobe, k, 1, &L)) return NAFP_ERR_UNSUPPORTED;
+    if (!ivf_dim_ok(dim) || M != PQ_M || !ivf_lut_ok(lut) || !ivf_search_layout(n_query, nlist, nprobe, k, 1, &L, wide)) return NAFP_ERR_UNSUPPORTED;
     if (n_query == 0) return NAFP_OK;
     if (workspace_bytes < L.total) return NAFP_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
     int rc = ivf_search_front(query, n_query, centroids, nlist, dim, L, ws, st);
     if (rc != NAFP_OK) return rc;
-    // fp32: table + residual + 4 wave bests; fp16: half the table + residual + 4 x K wave results
-    const int lds = lut == NAFP_IVF_LUT_F32 ? (PQ_M * PQ_KS + 256) * 4 + 4 * 8 : PQ_M * PQ_KS * 2 + 256 * 4 + 4 * L.K * 8;
-    const dim3 grid((unsigned)L.n_pairs, (unsigned)L.parts);
-    const int* qm = (const int*)(ws + L.o_qmap);
-    const int* pl = (const int*)(ws + L.o_plist);
-    float* pk = (float*)(ws + L.o_pk);
-    int* pi = (int*)(ws + L.o_pi);
-#define NAFP_PQ_SCAN(KERNEL_, DS_, K_)                                                                                          \
-    {                                                                                                                           \
-        NAFP_HIP_CHECK(hipFuncSetAttribute((const void*)KERNEL_<DS_, K_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));       \
-        KERNEL_<DS_, K_><<<grid, 256, lds, st>>>(query, qm, pl, centroids, pq_centroids, codes_sorted, offsets, ids, L.parts, pk, pi); \
-    }
-#define NAFP_PQ_SCAN_K(KERNEL_, DS_) { if (L.K == 20) NAFP_PQ_SCAN(KERNEL_, DS_, 20) else NAFP_PQ_SCAN(KERNEL_, DS_, 32) }
-#define NAFP_PQ_SCAN_D(KERNEL_)                                                                                                 \
-    { if (dsub == 1) NAFP_PQ_SCAN_K(KERNEL_, 1) else if (dsub == 2) NAFP_PQ_SCAN_K(KERNEL_, 2) else NAFP_PQ_SCAN_K(KERNEL_, 4) }
-    const int dsub = dim / PQ_M;
-    if (lut == NAFP_IVF_LUT_F32) NAFP_PQ_SCAN_D(ivf_pq_scan_kernel) else NAFP_PQ_SCAN_D(ivf_pq_scan_f16_kernel)
-#undef NAFP_PQ_SCAN_D
-#undef NAFP_PQ_SCAN_K
-#undef NAFP_PQ_SCAN
+    const bool f32 = lut == NAFP_IVF_LUT_F32;
+    hipError_t err = hipSuccess;
+    // the wide scan takes K at run time (k_arg), the narrow ones have it compiled in
+    auto scan = [&](auto kernel, int lds, auto... k_arg) {
+        err = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (err != hipSuccess) return;
+        kernel<<<dim3((unsigned)L.n_pairs, (unsigned)L.parts), 256, lds, st>>>(
+            query, (const int*)(ws + L.o_qmap), (const int*)(ws + L.o_plist), centroids, pq_centroids, codes_sorted, offsets, ids, L.parts,
+            k_arg..., (float*)(ws + L.o_pk), (int*)(ws + L.o_pi));
+    };
+    ivf_with_dsub(dim, [&](auto ds) {
+        if (wide)
+            ivf_with_either<0, 1>(f32, [&](auto lt) { scan(ivf_pq_scan_wide_kernel<ds(), lt()>, ivf_pq_scan_wide_lds_bytes(lt()), L.K); });
+        else
+            ivf_with_either<20, 32>(L.K == 20, [&](auto kk) {
+                if (f32) scan(ivf_pq_scan_kernel<ds(), kk()>, ivf_pq_scan_lds_bytes());
+                else     scan(ivf_pq_scan_f16_kernel<ds(), kk()>, ivf_pq_scan_f16_lds_bytes(kk()));
+            });
+    });
+    NAFP_HIP_CHECK(err);
     NAFP_LAUNCH_CHECK();
     return ivf_search_merge(L, ws, n_query, nullptr, nullptr, query, dim, 1, out_dist, out_ids, k, st);
+}
+
+extern "C" int nafp_ivf_pq_search_ex(const float* query, int64_t n_query, const float* centroids, int nlist, int dim, int nprobe,
+                                     const float* pq_centroids, int M, const uint8_t* codes_sorted, const int32_t* offsets,
+                                     const int32_t* ids, int k, float* out_dist, int32_t* out_ids, int lut, void* workspace,
+                                     int64_t workspace_bytes, void* stream) {
+    return ivf_pq_search_run(false, query, n_query, centroids, nlist, dim, nprobe, pq_centroids, M, codes_sorted, offsets, ids, k, out_dist,
+                             out_ids, lut, workspace, workspace_bytes, stream);
 }
 
 extern "C" int nafp_ivf_pq_search(const float* query, int64_t n_query, const float* centroids, int nlist, int dim, int nprobe,
@@ -1070,14 +1099,11 @@ extern "C" int nafp_ivf_pq_adc_tables(const float* query, int64_t n_query, const
     if (n_pairs == 0) return NAFP_OK;
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)n_pairs;
-#define NAFP_PQ_TABLES(DS_)                                                                                                     \
-    {                                                                                                                           \
-        if (lut == NAFP_IVF_LUT_F32) ivf_pq_adc_tables_kernel<DS_, 0><<<grid, 256, 0, st>>>(query, n_query, pair_query, pair_list, centroids, nlist, pq_centroids, out); \
-        else                         ivf_pq_adc_tables_kernel<DS_, 1><<<grid, 256, 0, st>>>(query, n_query, pair_query, pair_list, centroids, nlist, pq_centroids, out); \
-    }
-    const int dsub = dim / PQ_M;
-    if (dsub == 1) NAFP_PQ_TABLES(1) else if (dsub == 2) NAFP_PQ_TABLES(2) else NAFP_PQ_TABLES(4)
-#undef NAFP_PQ_TABLES
+    ivf_with_dsub(dim, [&](auto ds) {
+        ivf_with_either<0, 1>(lut == NAFP_IVF_LUT_F32, [&](auto lt) {
+            ivf_pq_adc_tables_kernel<ds(), lt()><<<grid, 256, 0, st>>>(query, n_query, pair_query, pair_list, centroids, nlist, pq_centroids, out);
+        });
+    });
     NAFP_LAUNCH_CHECK();
     return NAFP_OK;
 }
@@ -1103,9 +1129,7 @@ extern "C" int nafp_ivf_refine_encode(const float* x, int64_t n, int dim, const 
     if (n == 0) return NAFP_OK;
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)((n + 255) / 256);
-    if (dim == 64)       ivf_refine_encode_kernel<16><<<grid, 256, 0, st>>>(x, n, refine_centroids, packed, codes);
-    else if (dim == 128) ivf_refine_encode_kernel<32><<<grid, 256, 0, st>>>(x, n, refine_centroids, packed, codes);
-    else                 ivf_refine_encode_kernel<64><<<grid, 256, 0, st>>>(x, n, refine_centroids, packed, codes);
+    ivf_with_dsub(dim, [&](auto ds) { ivf_refine_encode_kernel<16 * ds()><<<grid, 256, 0, st>>>(x, n, refine_centroids, packed, codes); });   // DR = d / 4
     NAFP_LAUNCH_CHECK();
     return NAFP_OK;
 }
@@ -1119,36 +1143,8 @@ extern "C" int nafp_ivf_pq_search_wide(const float* query, int64_t n_query, cons
                                        const float* pq_centroids, int M, const uint8_t* codes_sorted, const int32_t* offsets,
                                        const int32_t* ids, int k1, float* out_dist, int32_t* out_ids, int lut, void* workspace,
                                        int64_t workspace_bytes, void* stream) {
-    if (!query || !centroids || !pq_centroids || !codes_sorted || !offsets || !ids || !out_dist || !out_ids || !workspace ||
-        n_query < 0 || nlist <= 0 || nprobe <= 0 || k1 <= 0)
-        return NAFP_ERR_INVALID_ARG;
-    IvfSearchLayout L;
-    if (!ivf_dim_ok(dim) || M != PQ_M || !ivf_lut_ok(lut) || !ivf_search_layout(n_query, nlist, nprobe, k1, 1, &L, true)) return NAFP_ERR_UNSUPPORTED;
-    if (n_query == 0) return NAFP_OK;
-    if (workspace_bytes < L.total) return NAFP_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    int rc = ivf_search_front(query, n_query, centroids, nlist, dim, L, ws, st);
-    if (rc != NAFP_OK) return rc;
-    // the table, the four wave buffers (over the residual's 1 KB), four counts
-    const int lds = (lut == NAFP_IVF_LUT_F32 ? PQ_M * PQ_KS * 4 : PQ_M * PQ_KS * 2) + 4 * WIDE_CAP * 8 + 16;
-    const dim3 grid((unsigned)L.n_pairs, (unsigned)L.parts);
-    const int* qm = (const int*)(ws + L.o_qmap);
-    const int* pl = (const int*)(ws + L.o_plist);
-    float* pk = (float*)(ws + L.o_pk);
-    int* pi = (int*)(ws + L.o_pi);
-#define NAFP_PQ_WIDE(DS_, LUT_)                                                                                                 \
-    {                                                                                                                           \
-        NAFP_HIP_CHECK(hipFuncSetAttribute((const void*)ivf_pq_scan_wide_kernel<DS_, LUT_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); \
-        ivf_pq_scan_wide_kernel<DS_, LUT_><<<grid, 256, lds, st>>>(query, qm, pl, centroids, pq_centroids, codes_sorted, offsets, ids, L.parts, L.K, pk, pi); \
-    }
-#define NAFP_PQ_WIDE_L(DS_) { if (lut == NAFP_IVF_LUT_F32) NAFP_PQ_WIDE(DS_, 0) else NAFP_PQ_WIDE(DS_, 1) }
-    const int dsub = dim / PQ_M;
-    if (dsub == 1) NAFP_PQ_WIDE_L(1) else if (dsub == 2) NAFP_PQ_WIDE_L(2) else NAFP_PQ_WIDE_L(4)
-#undef NAFP_PQ_WIDE_L
-#undef NAFP_PQ_WIDE
-    NAFP_LAUNCH_CHECK();
-    return ivf_search_merge(L, ws, n_query, nullptr, nullptr, query, dim, 1, out_dist, out_ids, k1, st);
+    return ivf_pq_search_run(true, query, n_query, centroids, nlist, dim, nprobe, pq_centroids, M, codes_sorted, offsets, ids, k1, out_dist,
+                             out_ids, lut, workspace, workspace_bytes, stream);
 }
 
 extern "C" int nafp_ivf_pqr_rerank(const float* query, int64_t n_query, int dim, const int32_t* cand_ids, int k1, const float* centroids,
@@ -1164,12 +1160,10 @@ extern "C" int nafp_ivf_pqr_rerank(const float* query, int64_t n_query, int dim,
     if (n_query == 0) return NAFP_OK;
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)n_query;
-#define NAFP_RERANK(DS_)                                                                                                        \
-    ivf_pqr_rerank_kernel<DS_><<<grid, WIDE_KMAX, 0, st>>>(query, cand_ids, k1, centroids, assign, pq_centroids, codes, refine_centroids, \
-                                                           refine_codes, n_rows, k, out_dist, out_ids);
-    const int dsub = dim / PQ_M;
-    if (dsub == 1) NAFP_RERANK(1) else if (dsub == 2) NAFP_RERANK(2) else NAFP_RERANK(4)
-#undef NAFP_RERANK
+    ivf_with_dsub(dim, [&](auto ds) {
+        ivf_pqr_rerank_kernel<ds()><<<grid, WIDE_KMAX, 0, st>>>(query, cand_ids, k1, centroids, assign, pq_centroids, codes, refine_centroids,
+                                                                refine_codes, n_rows, k, out_dist, out_ids);
+    });
     NAFP_LAUNCH_CHECK();
     return NAFP_OK;
 }

@@ -180,6 +180,11 @@ def _as_device(x, device):
     return torch.from_numpy(np.array(x, dtype=np.float32)).to(device)
 
 
+def _codebook(c, shape, device):
+    """Explicit codewords (numpy or tensor, any shape of the right size) as a float32 tensor of `shape` of their own on the device."""
+    return _as_device(c.reshape(shape) if torch.is_tensor(c) else np.asarray(c, dtype=np.float32).reshape(shape), device).clone()
+
+
 def kmeans(x, init, niter=COARSE_ITERS, seed=DEFAULT_SEED, device=None):
     """k-means on the device from an explicit initialisation init (k, d): the coarse quantizer's training loop.
     Returns (centroids (k, d) float32 numpy, final cluster sizes (k,))."""
@@ -278,14 +283,23 @@ class _IVFBase:
                 self._lists = self._build_lists(offsets.reshape(-1), ids.reshape(-1))
         return self._lists
 
-    def search_device(self, q, k):
-        """q: (nq, d) CUDA float32 -> (D, I) CUDA tensors (float32, int32)."""
+    def _search_inputs(self, q, k):
+        """What every search starts with: the queries as contiguous float32 on the device, k and the index checked, the lists."""
         q = _lib.require_cuda(q, 'q').float().contiguous()
         if k > MAX_K or k < 1:
             raise NotImplementedError(f'k = {k} (the HIP search keeps k <= {MAX_K} results per query)')
         if self.ntotal == 0:
             raise ValueError('empty index')
-        lists = self._prepare()
+        return q, self._prepare()
+
+    def _search_numpy(self, search_device, q, k):
+        """numpy in, numpy out of a device search: distances float32, ids int64."""
+        qd = torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32)).to(self.device)
+        return tuple(t.cpu().numpy() if t.is_floating_point() else t.cpu().numpy().astype(np.int64) for t in search_device(qd, k))
+
+    def search_device(self, q, k):
+        """q: (nq, d) CUDA float32 -> (D, I) CUDA tensors (float32, int32)."""
+        q, lists = self._search_inputs(q, k)
         nq = q.shape[0]
         D = self._dev.empty((nq, k), torch.float32)
         I = self._dev.empty((nq, k), torch.int32)
@@ -299,9 +313,7 @@ class _IVFBase:
 
     def search(self, q, k):
         """faiss signature: numpy in, (D float32, I int64) numpy out."""
-        qd = torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32)).to(self.device)
-        D, I = self.search_device(qd, k)
-        return D.cpu().numpy(), I.cpu().numpy().astype(np.int64)
+        return self._search_numpy(self.search_device, q, k)
 
     def reconstruct_n(self, i0, n):
         return self._flat.reconstruct_n(i0, n)
@@ -358,7 +370,6 @@ class IVFFlatIndex(_IVFBase):
                    'ivf_flat_search')
 
 
-
 class IVFPQIndex(_IVFBase):
     """faiss.IndexIVFPQ(quantizer, d, nlist, M, nbits) with by_residual: M = 64 sub-quantizers of 2^nbits = 256 codewords of
     the residual to the coarse centroid.  `lut`: the precision of the ADC tables of a search, 'f32' (default) or 'f16' (the
@@ -396,8 +407,7 @@ class IVFPQIndex(_IVFBase):
 
     def set_params(self, centroids, pq_centroids):
         self.centroids = _as_device(centroids, self.device).clone()
-        self.pq_centroids = _as_device(np.asarray(pq_centroids, dtype=np.float32).reshape(self.M, PQ_KS, self.dsub) if not torch.is_tensor(pq_centroids)
-                                       else pq_centroids.reshape(self.M, PQ_KS, self.dsub), self.device).clone()
+        self.pq_centroids = _codebook(pq_centroids, (self.M, PQ_KS, self.dsub), self.device)
         self._lists = None
 
     def train(self, x, init=None, pq_init=None):
@@ -422,8 +432,7 @@ class IVFPQIndex(_IVFBase):
                 pick = torch.from_numpy(rng.permutation(r.shape[0])[:PQ_KS]).to(self.device)
                 pq = r[pick].reshape(PQ_KS, self.M, self.dsub).transpose(0, 1).contiguous()
             else:
-                pq = _as_device(np.asarray(pq_init, dtype=np.float32).reshape(self.M, PQ_KS, self.dsub) if not torch.is_tensor(pq_init)
-                                else pq_init.reshape(self.M, PQ_KS, self.dsub), self.device).clone()
+                pq = _codebook(pq_init, (self.M, PQ_KS, self.dsub), self.device)
             dev.kmeans(r, pq, PQ_KS, self.M, PQ_ITERS, rng_for(self.seed, STREAM_PQ_SPLIT), lambda c: (dev.pq_encode(r, None, None, c), 1))
         self.pq_centroids = pq
         return r
@@ -499,13 +508,9 @@ class IVFPQRIndex(IVFPQIndex):
         return (f'IVFPQR (HIP; nlist {self.nlist}, M {self.M}, nbits {self.nbits}, refine {self.M_refine} x {self.nbits_refine} bits, '
                 f'k_factor {self._k_factor}, nprobe {self._nprobe}{tables})')
 
-    def _refine_shape(self, c):
-        shape = (REFINE_M, REFINE_KS, self.dsub_refine)
-        return _as_device(c.reshape(shape) if torch.is_tensor(c) else np.asarray(c, dtype=np.float32).reshape(shape), self.device).clone()
-
     def set_params(self, centroids, pq_centroids, refine_centroids):
         super().set_params(centroids, pq_centroids)
-        self.refine_centroids = self._refine_shape(refine_centroids)
+        self.refine_centroids = _codebook(refine_centroids, (REFINE_M, REFINE_KS, self.dsub_refine), self.device)
 
     def train(self, x, init=None, pq_init=None, refine_init=None):
         """As IVFPQIndex.train, then the refine quantizer on the PQ stage's own training residuals r: k-means (16 codewords in each
@@ -521,7 +526,7 @@ class IVFPQRIndex(IVFPQIndex):
                 pick = torch.from_numpy(rng_for(self.seed, STREAM_REFINE).permutation(r2.shape[0])[:REFINE_KS]).to(self.device)
                 rf = r2[pick].reshape(REFINE_KS, REFINE_M, self.dsub_refine).transpose(0, 1).contiguous()
             else:
-                rf = self._refine_shape(refine_init)
+                rf = _codebook(refine_init, (REFINE_M, REFINE_KS, self.dsub_refine), self.device)
             dev.kmeans(r2, rf, REFINE_KS, REFINE_M, PQ_ITERS, rng_for(self.seed, STREAM_REFINE_SPLIT),
                        lambda c: (dev.refine_encode(r2, c, False), 1))
         self.refine_centroids = rf
@@ -543,12 +548,7 @@ class IVFPQRIndex(IVFPQIndex):
 
     def search_stages_device(self, q, k):
         """q: (nq, d) CUDA -> (D1, I1, D, I) CUDA: the first stage's k * k_factor candidates and the k re-ranked results."""
-        q = _lib.require_cuda(q, 'q').float().contiguous()
-        if k > MAX_K or k < 1:
-            raise NotImplementedError(f'k = {k} (the HIP search keeps k <= {MAX_K} results per query)')
-        if self.ntotal == 0:
-            raise ValueError('empty index')
-        L = self._prepare()
+        q, L = self._search_inputs(q, k)
         nq, k1, lib = q.shape[0], int(k) * self._k_factor, self._dev.lib
         D, I = self._dev.empty((nq, k), torch.float32), self._dev.empty((nq, k), torch.int32)
         D1, I1 = self._dev.empty((nq, k1), torch.float32), self._dev.empty((nq, k1), torch.int32)
@@ -570,6 +570,4 @@ class IVFPQRIndex(IVFPQIndex):
 
     def search_stages(self, q, k):
         """numpy in, (D1, I1, D, I) numpy out (ids int64): `search` plus the first stage it re-ranked."""
-        qd = torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32)).to(self.device)
-        D1, I1, D, I = self.search_stages_device(qd, k)
-        return D1.cpu().numpy(), I1.cpu().numpy().astype(np.int64), D.cpu().numpy(), I.cpu().numpy().astype(np.int64)
+        return self._search_numpy(self.search_stages_device, q, k)

@@ -843,6 +843,43 @@ int nafp_search_seq_match(const float* query, int64_t n_query, const float* inde
                           int64_t n_tasks, int max_len, int n_out, int32_t* out_ids, float* out_scores,
                           int32_t* out_n_cand, void* stream);
 
+/* Identification: the track-aware sequence matcher.  `index` is the row array of a library of tracks laid end to end,
+ * track_first (n_tracks + 1, strictly increasing, [0] == 0, [n_tracks] == n_index) the first row of each track.  One task t =
+ * one analysis window of one recording: rows task_q0[t] .. of `query`, topk_ids (n_query, k) = the segment search result
+ * per query row.  All array arguments are device pointers; no workspace.  Unlike nafp_search_seq_match, an alignment may be
+ * negative or lie before its track (a recording that starts before the track does), a window is scored only where it
+ * overlaps its track (never against the next track's rows), votes are counted, and a task may have 8192 slots.
+ *   - len_t = min(task_len[t], max_len, n_query - task_q0[t]); a task with task_q0[t] outside [0, n_query) or len_t <= 0
+ *     has no candidates;
+ *   - candidates: every slot (i < len_t, j < k) with id = topk_ids[task_q0[t] + i, j] in [0, n_index) gives the pair
+ *     (tr, a): tr the track with first[tr] <= id < first[tr + 1], a = id - i the alignment, the index row segment 0 of the
+ *     window falls on (any sign).  A candidate is a DISTINCT pair; the same a through two tracks is two candidates;
+ *   - votes v(tr, a): the number of slots that gave the pair;
+ *   - overlap: i0 = max(0, first[tr] - a), i1 = min(len_t, first[tr + 1] - a), n_ov = i1 - i0 (>= 1).  A candidate with
+ *     n_ov < min(min_overlap, len_t) or v < min_votes is dropped;
+ *   - shortlist: the n_short best of the rest by votes descending, track ascending, a ascending; out_n_cand[t] (or NULL)
+ *     counts the rest BEFORE this cut;
+ *   - score of a shortlisted candidate = mean_{i0 <= i < i1} query[task_q0[t] + i] . index[a + i]: the bits of
+ *     nafp_search_seq_scores for task_q0 = task_q0[t] + i0, task_len = n_ov, cand = a + i0 (the one summation order of the
+ *     sequence score).  A NaN or -inf score drops the candidate;
+ *   - out_track / out_align / out_score / out_votes / out_overlap (n_tasks, n_out): the n_out best by score descending,
+ *     track ascending, a ascending; padding track -1, align 0, score -inf, votes 0, overlap 0;
+ *   - bit-identical from run to run; a task's rows do not depend on what else is in the launch.
+ * The kernel reads only rows [0, n_index) of `index` whatever track_first holds; nafp_search_identify_check_tracks_host
+ * (host pointer) is the check of the table: NAFP_ERR_INVALID_ARG unless it is as stated above.
+ * Status, before any GPU call: NAFP_ERR_INVALID_ARG for a null pointer (out_n_cand excepted) or a negative size;
+ * NAFP_ERR_UNSUPPORTED for dim outside 64 / 128 / 256, k outside 1..32, max_len < 1, k * max_len > 8192, n_short outside
+ * 1..256, n_out outside 1..32 or above n_short, min_overlap < 1, min_votes < 1, n_index > 2^31 - 2^14, n_tracks outside
+ * 1..2^24 (n_query, n_tasks >= 2^31 likewise); n_tasks == 0 returns NAFP_OK without a launch. */
+int nafp_search_identify(const float* query, int64_t n_query, const float* index, int64_t n_index, int dim,
+                         const int32_t* topk_ids, int k,
+                         const int32_t* task_q0, const int32_t* task_len, int64_t n_tasks, int max_len,
+                         const int32_t* track_first, int n_tracks,
+                         int min_overlap, int min_votes, int n_short, int n_out,
+                         int32_t* out_track, int32_t* out_align, float* out_score,
+                         int32_t* out_votes, int32_t* out_overlap, int32_t* out_n_cand, void* stream);
+int nafp_search_identify_check_tracks_host(const int32_t* track_first_host, int n_tracks, int64_t n_index);
+
 /* ---------------------------------------------------------------------------------------------
  * Approximate indexes: IVF-Flat and IVF-PQ (faiss IndexIVFFlat / IndexIVFPQ as
  * eval/utils/get_index_faiss.py:64-80 builds them; opt-in from eval_faiss.py).  Building blocks of

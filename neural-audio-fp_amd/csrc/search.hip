@@ -19,6 +19,7 @@
 //   ivf_flat_scan_kernel<D,K>  the same body over one inverted list's rows for the queries that probe it (ivf.hip)
 //   search_seq_score_kernel<D> mean_i q[t+i] . x[c+i] for candidate sequence starts c (eval_faiss.py:221-230)
 //   search_seq_match_kernel<D> top-k ids -> offset-compensated unique candidates -> scores -> the n_out best (eval_faiss.py:213-232)
+//   search_identify_kernel<D>  top-k ids -> (track, alignment) candidates with votes -> overlap-only scores -> the n_out best (eval/identify.py)
 #include "nafp_common.h"
 
 #include <algorithm>
@@ -443,6 +444,187 @@ __global__ __launch_bounds__(256) void search_seq_match_kernel(
     }
 }
 
+// Identification: the track-aware sequence matcher, one workgroup of 256 threads per task (include/nafp.h,
+// nafp_search_identify, states the contract):
+//   1. gather    slot (i, j) -> key = track << 32 | (a + IDENT_BIAS), a = topk[q0 + i, j] - i (any sign), track by one binary
+//                search of track_first; absent / out-of-range ids -> IDENT_NONE; the slots are padded to P, the power of two that
+//                holds this task's k * len slots
+//   2. sort      bitonic, ascending, in LDS: equal (track, a) pairs become runs, IDENT_NONE goes to the end
+//   3. compact   the first element of each run and its position, by ballot and prefix counts (no atomic slot allocation); the
+//                next run's position (or the number of valid slots) minus its own is the run's length = the votes
+//   4. filter    overlap with the track and the votes against the two minima; a survivor n becomes the 32-bit selection key
+//                (8192 - votes) << 13 | n -- the unique list is in (track, a) order, so n breaks the vote ties as the contract
+//                says -- every other slot 0xffffffff; the survivors are counted by ballot
+//   5. shortlist a second bitonic sort, of the selection keys: the first n_short are the shortlist
+//   6. score     the four waves walk the shortlist, seq_score_wave once each over the overlap only
+//   7. select    wave 0: n_out rounds of arg-max by (score descending, key ascending) below the previous round's
+// LDS: P keys + P ints = 12 P bytes (96 KB at the 8192-slot maximum, 6 KB for the default 20 x 20 window) + 6 KB static.
+constexpr unsigned long long IDENT_NONE = ~0ull;
+constexpr int IDENT_BIAS = 1 << 14;               // a >= -(8192 - 1), so a + bias > 0; n_index <= 2^31 - 2^14 keeps it in 31 bits
+constexpr int IDENT_MAX_SLOTS = 8192;
+constexpr int IDENT_MAX_SHORT = 256;
+
+template <typename T>
+__device__ __forceinline__ void bitonic_sort_lds(T* v, int P, int tid) {
+    for (int kk = 2; kk <= P; kk <<= 1)
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (P >> 1); t += 256) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;
+                const T a = v[i], b = v[p];
+                if ((a > b) == ((i & kk) == 0)) { v[i] = b; v[p] = a; }
+            }
+            __syncthreads();
+        }
+}
+
+// the overlap [i0, i1) of a window of len rows laid at alignment a with track tr, clipped to the rows the index has
+__device__ __forceinline__ void ident_overlap(const int* __restrict__ first, int n_tracks, int64_t N, int tr, int a, int len,
+                                              int* i0, int* i1) {
+    const int64_t lo = std::max<int64_t>(first[tr], 0), hi = std::min<int64_t>(first[tr + 1], N);
+    *i0 = (int)std::max<int64_t>(0, lo - a);
+    *i1 = (int)std::max<int64_t>(*i0, std::min<int64_t>(len, hi - a));
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void search_identify_kernel(
+        const float* __restrict__ Q, int n_query, const float* __restrict__ X, int64_t N, const int* __restrict__ topk, int k,
+        const int* __restrict__ task_q0, const int* __restrict__ task_len, int max_len, const int* __restrict__ first, int n_tracks,
+        int min_overlap, int min_votes, int n_short, int n_out, int* __restrict__ out_track, int* __restrict__ out_align,
+        float* __restrict__ out_score, int* __restrict__ out_votes, int* __restrict__ out_overlap, int* __restrict__ out_n_cand,
+        int p_max) {
+    extern __shared__ unsigned long long ident_keys[];           // [p_max] keys, then [p_max] unsigned
+    unsigned* aux = (unsigned*)(ident_keys + p_max);
+    __shared__ unsigned long long sl_key[IDENT_MAX_SHORT];
+    __shared__ unsigned sl_su[IDENT_MAX_SHORT];                  // the score as an ordered unsigned; 0: dropped
+    __shared__ float sl_score[IDENT_MAX_SHORT];
+    __shared__ int sl_votes[IDENT_MAX_SHORT], sl_ov[IDENT_MAX_SHORT];
+    __shared__ int wcnt[4], wval[4];
+    const int task = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int q0 = task_q0[task];
+    int len = 0;
+    if (q0 >= 0 && q0 < n_query) len = std::max(0, std::min(std::min(task_len[task], max_len), n_query - q0));
+    const int S = k * len;                                         // <= k * max_len <= p_max
+    int P = 1;
+    while (P < S) P <<= 1;
+
+    // 1. gather
+    for (int s = tid; s < P; s += 256) {
+        unsigned long long key = IDENT_NONE;
+        if (s < S) {
+            const int i = s / k;
+            const int id = topk[(int64_t)(q0 + i) * k + (s - i * k)];
+            if (id >= 0 && id < N) {
+                int lo = 0, hi = n_tracks - 1;                       // the last track whose first row is <= id
+                while (lo < hi) {
+                    const int mid = (lo + hi + 1) >> 1;
+                    if (first[mid] <= id) lo = mid; else hi = mid - 1;
+                }
+                key = ((unsigned long long)(unsigned)lo << 32) | (unsigned)(id - i + IDENT_BIAS);
+            }
+        }
+        ident_keys[s] = key;
+    }
+    __syncthreads();
+    // 2. sort
+    bitonic_sort_lds(ident_keys, P, tid);
+    // 3. compact the run heads and their positions, 256 slots at a time.  Head i moves to a slot <= i, and slot base - 1, which the
+    //    next pass reads as its first predecessor, can only have been written by element base - 1 itself.
+    int n_uniq = 0, n_valid = 0;
+    for (int base = 0; base < P; base += 256) {
+        const int i = base + tid;
+        unsigned long long c = IDENT_NONE;
+        bool head = false;
+        if (i < P) { c = ident_keys[i]; head = c != IDENT_NONE && (i == 0 || ident_keys[i - 1] != c); }
+        const unsigned long long m = __ballot(head), mv = __ballot(c != IDENT_NONE);
+        if (lane == 0) { wcnt[wave] = __popcll(m); wval[wave] = __popcll(mv); }
+        __syncthreads();
+        int before = n_uniq;
+        for (int w = 0; w < wave; ++w) before += wcnt[w];
+        if (head) {
+            const int pos = before + __popcll(m & ((1ull << lane) - 1ull));
+            ident_keys[pos] = c;
+            aux[pos] = (unsigned)i;
+        }
+        n_uniq += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        n_valid += wval[0] + wval[1] + wval[2] + wval[3];
+        __syncthreads();
+    }
+    // 4. votes, overlap, the two minima -> selection keys in place of the positions
+    int P2 = 1;
+    while (P2 < n_uniq) P2 <<= 1;                                  // <= P: n_uniq <= S
+    const int need_ov = std::min(min_overlap, len);
+    int n_cand = 0;
+    for (int base = 0; base < P2; base += 256) {
+        const int n = base + tid;
+        unsigned sel = 0xffffffffu;
+        if (n < n_uniq) {
+            const int v = (int)(n + 1 < n_uniq ? aux[n + 1] : (unsigned)n_valid) - (int)aux[n];
+            const unsigned long long key = ident_keys[n];
+            int i0, i1;
+            ident_overlap(first, n_tracks, N, (int)(key >> 32), (int)(unsigned)key - IDENT_BIAS, len, &i0, &i1);
+            if (i1 - i0 >= need_ov && i1 > i0 && v >= min_votes) sel = ((unsigned)(IDENT_MAX_SLOTS - v) << 13) | (unsigned)n;
+        }
+        const unsigned long long m = __ballot(sel != 0xffffffffu);
+        if (lane == 0) wcnt[wave] = __popcll(m);
+        __syncthreads();                                           // every aux[n + 1] of this pass is read
+        if (n < P2) aux[n] = sel;
+        n_cand += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        __syncthreads();
+    }
+    if (tid == 0 && out_n_cand) out_n_cand[task] = n_cand;
+    // 5. shortlist
+    bitonic_sort_lds(aux, P2, tid);
+    const int n_sl = std::min(n_short, n_cand);
+    // 6. score each shortlisted candidate once, over its overlap
+    for (int m = wave; m < n_sl; m += 4) {
+        const unsigned sel = aux[m];
+        const unsigned long long key = ident_keys[sel & 8191u];
+        const int a = (int)(unsigned)key - IDENT_BIAS;
+        int i0, i1;
+        ident_overlap(first, n_tracks, N, (int)(key >> 32), a, len, &i0, &i1);
+        const float sc = seq_score_wave<D>(Q, X, q0 + i0, a + i0, i1 - i0, lane);
+        if (lane == 0) {
+            const bool keep = !(sc != sc) && sc != -INFINITY;
+            unsigned u = __float_as_uint(sc == 0.f ? 0.f : sc);       // -0 ranks with +0
+            u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;
+            sl_key[m] = key; sl_su[m] = keep ? u : 0u; sl_score[m] = sc;
+            sl_votes[m] = IDENT_MAX_SLOTS - (int)(sel >> 13); sl_ov[m] = i1 - i0;
+        }
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    // 7. n_out rounds of arg-max: score descending, then (track, a) ascending.  The keys are distinct, so the order is total.
+    unsigned long long prev_su = 1ull << 32, prev_key = 0ull;      // above every candidate
+    for (int r = 0; r < n_out; ++r) {
+        unsigned long long b_su = 0ull, b_key = IDENT_NONE;
+        int b_m = -1;
+        for (int m = lane; m < n_sl; m += 64) {
+            const unsigned long long su = sl_su[m], key = sl_key[m];
+            const bool below = su < prev_su || (su == prev_su && key > prev_key);
+            const bool better = su > b_su || (su == b_su && key < b_key);
+            if (su != 0ull && below && better) { b_su = su; b_key = key; b_m = m; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long o_su = __shfl_xor(b_su, o, 64), o_key = __shfl_xor(b_key, o, 64);
+            const int o_m = __shfl_xor(b_m, o, 64);
+            if (o_su > b_su || (o_su == b_su && o_key < b_key)) { b_su = o_su; b_key = o_key; b_m = o_m; }
+        }
+        if (lane == 0) {
+            const int64_t o = (int64_t)task * n_out + r;
+            const bool got = b_m >= 0;
+            out_track[o] = got ? (int)(b_key >> 32) : -1;
+            out_align[o] = got ? (int)(unsigned)b_key - IDENT_BIAS : 0;
+            out_score[o] = got ? sl_score[b_m] : -INFINITY;
+            out_votes[o] = got ? sl_votes[b_m] : 0;
+            out_overlap[o] = got ? sl_ov[b_m] : 0;
+        }
+        if (b_m < 0) { prev_su = 0ull; prev_key = IDENT_NONE; }   // the candidates ran out: the later rounds find nothing
+        else { prev_su = b_su; prev_key = b_key; }
+    }
+}
+
 template <int D, int K>
 static int launch_topk(const float* Q, int nq, const float* X, const float* hn, int64_t N, float* pk, int* pi, int splits,
                        int tps, hipStream_t st) {
@@ -564,7 +746,49 @@ extern "C" int nafp_search_seq_match(const float* query, int64_t n_query, const 
     return NAFP_OK;
 }
 
-// ---- in-training mini search (model/utils/mini_search_subroutines.py:28-220) ------------------------------
+extern "C" int nafp_search_identify_check_tracks_host(const int32_t* track_first_host, int n_tracks, int64_t n_index) {
+    if (!track_first_host || n_tracks < 1 || n_index < 1 || n_index >= ((int64_t)1 << 31)) return NAFP_ERR_INVALID_ARG;
+    if (track_first_host[0] != 0 || track_first_host[n_tracks] != n_index) return NAFP_ERR_INVALID_ARG;
+    for (int t = 0; t < n_tracks; ++t)
+        if (track_first_host[t + 1] <= track_first_host[t]) return NAFP_ERR_INVALID_ARG;
+    return NAFP_OK;
+}
+
+extern "C" int nafp_search_identify(const float* query, int64_t n_query, const float* index, int64_t n_index, int dim,
+                                    const int32_t* topk_ids, int k, const int32_t* task_q0, const int32_t* task_len,
+                                    int64_t n_tasks, int max_len, const int32_t* track_first, int n_tracks, int min_overlap,
+                                    int min_votes, int n_short, int n_out, int32_t* out_track, int32_t* out_align,
+                                    float* out_score, int32_t* out_votes, int32_t* out_overlap, int32_t* out_n_cand, void* stream) {
+    if (!query || !index || !topk_ids || !task_q0 || !task_len || !track_first || !out_track || !out_align || !out_score ||
+        !out_votes || !out_overlap || n_query < 0 || n_index < 0 || n_tasks < 0)
+        return NAFP_ERR_INVALID_ARG;
+    if (dim != 64 && dim != 128 && dim != 256) return NAFP_ERR_UNSUPPORTED;
+    if (k < 1 || k > 32 || max_len < 1 || k * (int64_t)max_len > IDENT_MAX_SLOTS) return NAFP_ERR_UNSUPPORTED;
+    if (n_short < 1 || n_short > IDENT_MAX_SHORT || n_out < 1 || n_out > 32 || n_out > n_short) return NAFP_ERR_UNSUPPORTED;
+    if (min_overlap < 1 || min_votes < 1 || n_tracks < 1 || n_tracks > (1 << 24)) return NAFP_ERR_UNSUPPORTED;
+    if (n_index > ((int64_t)1 << 31) - IDENT_BIAS || n_query >= ((int64_t)1 << 31) || n_tasks >= ((int64_t)1 << 31)) return NAFP_ERR_UNSUPPORTED;
+    if (n_tasks == 0) return NAFP_OK;
+    int p_max = 1;
+    while (p_max < k * max_len) p_max <<= 1;
+    const int lds = p_max * 12;                                    // sized by this task set, not by the limit: 96 KB only at 8192 slots
+    hipStream_t st = (hipStream_t)stream;
+#define NAFP_IDENT(D_)                                                                                                          \
+    {                                                                                                                           \
+        if (lds > 48 * 1024)                                                                                                    \
+            NAFP_HIP_CHECK(hipFuncSetAttribute((const void*)search_identify_kernel<D_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); \
+        search_identify_kernel<D_><<<(unsigned)n_tasks, 256, lds, st>>>(query, (int)n_query, index, n_index, topk_ids, k, task_q0,  \
+            task_len, max_len, track_first, n_tracks, min_overlap, min_votes, n_short, n_out, out_track, out_align, out_score,    \
+            out_votes, out_overlap, out_n_cand, p_max);                                                                         \
+    }
+    if (dim == 128) NAFP_IDENT(128)
+    else if (dim == 256) NAFP_IDENT(256)
+    else NAFP_IDENT(64)
+#undef NAFP_IDENT
+    NAFP_LAUNCH_CHECK();
+    return NAFP_OK;
+}
+
+// ---- in-training mini search(model/utils/mini_search_subroutines.py:28-220) ------------------------------
 namespace nafp {
 
 // scores[q, x] = max(|q|^2 + |x|^2 - 2 q.x, 0)  (mode 0)  or  q.x  (mode 1); any dim (1024 for the un-projected

@@ -159,6 +159,41 @@ class FlatL2Index:
                                                        _lib.current_stream()), 'search_seq_match')
         return ids, scores, n_cand
 
+    def identify(self, q, topk_ids, task_q0, task_len, track_first, n_out=1, n_short=32, min_overlap=4, min_votes=2, max_len=None):
+        """The track-aware sequence match in one launch (nafp_search_identify, include/nafp.h): per task (one analysis window of a
+        recording) the distinct (track, alignment) pairs of topk_ids (nq, k) int32 with their votes, the n_short best by votes scored
+        over their overlap with the track only, and the n_out best by score.  q (nq, d) CUDA float32, task_q0 / task_len (T,) int32
+        CUDA, track_first (n_tracks + 1,) int32 on the host (numpy or CPU tensor): the first row of each track, checked here
+        (nafp_search_identify_check_tracks_host) before anything runs; `max_len` defaults to the maximum of task_len.  Returns
+        (track, align, score, votes, overlap) (T, n_out) and n_cand (T,) on the device; padding is track -1, align 0, score -inf,
+        votes 0, overlap 0."""
+        q = _lib.require_cuda(q, 'q')
+        first = np.ascontiguousarray(track_first.numpy() if torch.is_tensor(track_first) else track_first)
+        if first.dtype != np.int32 or first.ndim != 1 or first.shape[0] < 2:
+            raise TypeError('identify: track_first (n_tracks + 1,) int32 on the host')
+        n_tracks = int(first.shape[0]) - 1
+        _lib.check(self._lib.nafp_search_identify_check_tracks_host(first.ctypes.data, n_tracks, self.ntotal), 'search_identify (track_first)')
+        T = int(task_q0.shape[0])
+        if q.dtype != torch.float32 or topk_ids.dtype != torch.int32 or task_q0.dtype != torch.int32 or task_len.dtype != torch.int32:
+            raise TypeError('identify: q float32, topk_ids / task_q0 / task_len int32')
+        if q.dim() != 2 or q.shape[1] != self.d or topk_ids.dim() != 2 or topk_ids.shape[0] != q.shape[0] or task_len.shape[0] != T:
+            raise ValueError('identify: q (nq, d), topk_ids (nq, k), task_q0 and task_len (T,)')
+        if max_len is None:
+            max_len = max(int(task_len.max()), 1) if T else 1
+        n_out = int(n_out)
+        track, align, votes, overlap = (torch.empty((T, n_out), dtype=torch.int32, device=self.device) for _ in range(4))
+        score = torch.empty((T, n_out), dtype=torch.float32, device=self.device)
+        n_cand = torch.empty((T,), dtype=torch.int32, device=self.device)
+        q, topk_ids, task_q0, task_len = q.contiguous(), topk_ids.contiguous(), task_q0.contiguous(), task_len.contiguous()
+        first_dev = torch.from_numpy(first).to(self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.nafp_search_identify(_lib.ptr(q), q.shape[0], _lib.ptr(self._x), self.ntotal, self.d, _lib.ptr(topk_ids),
+                                                      int(topk_ids.shape[1]), _lib.ptr(task_q0), _lib.ptr(task_len), T, int(max_len),
+                                                      _lib.ptr(first_dev), n_tracks, int(min_overlap), int(min_votes), int(n_short), n_out,
+                                                      _lib.ptr(track), _lib.ptr(align), _lib.ptr(score), _lib.ptr(votes), _lib.ptr(overlap),
+                                                      _lib.ptr(n_cand), _lib.current_stream()), 'search_identify')
+        return track, align, score, votes, overlap, n_cand
+
 
 def seq_match_enabled():
     """NAFP_SEQ_MATCH=1: the evaluation ranks the sequence candidates on the device (`FlatL2Index.sequence_match`) instead of on

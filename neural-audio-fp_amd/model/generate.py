@@ -158,6 +158,24 @@ def get_data_source(cfg, source_root_dir, skip_dummy):
     return ds
 
 
+def track_table_enabled():
+    """NAFP_TRACK_TABLE=1: `generate` writes <key>_tracks.json next to every <key>.mm that comes from a `SegmentSource` -- which
+    file each row belongs to, what `run.py identify` names its matches by.  Opt-in: without it nothing new is written."""
+    return os.environ.get('NAFP_TRACK_TABLE', '') == '1'
+
+
+def track_table(source):
+    """The table of a `SegmentSource`: rows [first[f], first[f + 1]) of its .mm file are the segments of files[f]."""
+    return {'hop_s': float(source.hop), 'duration_s': float(source.duration), 'fs': int(source.fs),
+            'files': [str(f) for f in source.fns], 'first': [int(v) for v in source.file_first]}
+
+
+def write_track_table(path, source):
+    import json
+    with open(path, 'w') as f:
+        json.dump(track_table(source), f, indent=1)
+
+
 def test_step(X, m_pre, m_fp, group_size=None):
     """generate.py:83-88: m_fp(m_pre(X)) (the layer's max subtraction is finished inside the encoder's first conv)."""
     m_fp.trainable = False
@@ -448,6 +466,8 @@ def generate_fingerprint(cfg, checkpoint_name, checkpoint_index, source_root_dir
             source_rates[key] = rates_summary(ds[key])
             print(f"'{key}': {source_rates[key]['resampled']} of {source_rates[key]['files']} files are resampled to "
                   f"{ds[key].fs} Hz mono on the device (rate x channels: files) {source_rates[key]['rates']}")
+        if rank == 0 and track_table_enabled() and hasattr(ds[key], 'file_first'):      # NAFP_TRACK_TABLE=1: row -> file, next to the .mm file
+            write_track_table(f'{output_root_dir}/{key}_tracks.json', ds[key])
         write_fingerprints(ds[key], embed, arr, bsz, rank, world)
         arr.flush()
         if getattr(files, 'flac', False) and key in source_rates:      # NAFP_INGEST_FLAC=1: summed on the device, read once here

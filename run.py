@@ -3,12 +3,15 @@
     python run.py train    NAME [-c CONFIG] [--max_epoch N] [--synthetic STEPS]
     python run.py generate NAME [INDEX] [-c CONFIG] [-s SRC_DIR] [-o OUT_DIR] [--skip_dummy]
     python run.py evaluate NAME INDEX [-c CONFIG] [-i ivfpq] [-t icassp] [--test_seq_len '1 3 5 9 11 19']
+    python run.py identify NAME INDEX PATH... [-c CONFIG] [-i L2] [--window 20] [--window_hop 10] [--k_probe 20] [--min_overlap 4]
+                           [--min_votes 2] [--n_short 32] [--min_score X] [--align_tol 1] [--output FILE]
 
 The command / argument / option surface equals the reference's run.py:13-162 (held to it by
 tests/test_golden_cli.py; one declared extension: `train --synthetic`; `evaluate -i` keeps the reference's default
 'ivfpq', which -- like every approximate faiss type -- is served by the exact search with a notice).
 Configuration files are looked up as ./config/<CONFIG>.yaml relative to the working directory, like the
-reference does.  All three commands run on the HIP library (include/nafp.h).
+reference does.  All three commands run on the HIP library (include/nafp.h).  `identify` is this project's own command: it is kept
+in a group of its own (`extensions`), so that `cli` stays the reference's surface, and `main` serves both.
 
 More than one GPU: start one process per GPU,
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 run.py generate NAME
@@ -144,5 +147,46 @@ def evaluate(checkpoint_name, checkpoint_index, config, index_type, test_seq_len
     eval_faiss(emb_dir, index_type=index_type, test_seq_len=test_seq_len, test_ids=test_ids, nogpu=nogpu)
 
 
+_IDENTIFY = [
+    (('--config', '-c'), dict(default='default', required=False, type=click.STRING)),
+    (('--index_type', '-i'), dict(default='L2', type=click.STRING,
+                                  help="the index the segment search runs on, as `evaluate -i` (same opt-in variables); the matcher "
+                                       'scores on the fp32 rows resident in HBM whatever the index')),
+    (('--window',), dict(default=20, type=click.INT, help='analysis window in segments (window x k_probe <= 8192)')),
+    (('--window_hop',), dict(default=10, type=click.INT, help='segments between the starts of consecutive windows')),
+    (('--k_probe',), dict(default=20, type=click.INT, help='search results per segment, 1..32')),
+    (('--min_overlap',), dict(default=4, type=click.INT, help='segments a window must share with a track')),
+    (('--min_votes',), dict(default=2, type=click.INT, help='search results that must agree on (track, alignment)')),
+    (('--n_short',), dict(default=32, type=click.INT, help='candidates scored per window, 1..256')),
+    (('--min_score',), dict(default=None, type=click.FLOAT, help='a window whose best score is below this is no match; default: no threshold')),
+    (('--align_tol',), dict(default=1, type=click.INT, help='segments by which the alignment of consecutive windows of one match may differ')),
+    (('--output',), dict(default=None, type=click.STRING, help='where identify.json goes; default next to the .mm files')),
+]
+
+
+@click.group()
+def extensions():
+    """Commands the reference does not have."""
+
+
+@extensions.command()
+@click.argument('checkpoint_name', required=True)
+@click.argument('checkpoint_index', required=True)
+@click.argument('paths', nargs=-1, required=True)
+@_with(_IDENTIFY)
+def identify(checkpoint_name, checkpoint_index, paths, config, index_type, window, window_hop, k_probe, min_overlap, min_votes,
+             n_short, min_score, align_tol, output):
+    """Name the track and the offset of unlabelled recordings (files or directories) against the fingerprints `generate` wrote
+    with NAFP_TRACK_TABLE=1."""
+    from neural_audio_fp_amd.eval.identify import identify as run_identify
+    cfg = load_config(config)
+    run_identify(cfg, checkpoint_name, checkpoint_index, list(paths), index_type=index_type, window=window, window_hop=window_hop,
+                 k_probe=k_probe, min_overlap=min_overlap, min_votes=min_votes, n_short=n_short, min_score=min_score,
+                 align_tol=align_tol, output=output)
+
+
+main = click.CommandCollection(sources=[cli, extensions], help=cli.help)
+
+
 if __name__ == '__main__':
-    cli()
+    main()

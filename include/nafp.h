@@ -806,7 +806,12 @@ int nafp_search_index_prepare(const float* index, int64_t n_index, int dim, floa
 
 int64_t nafp_search_workspace_bytes(int64_t n_query, int64_t n_index, int k);
 /* out_dist / out_ids (n_query, k): the k smallest squared L2 distances and their row ids, nearest
- * first; equal distances: smaller id first; fewer than k rows: id -1, distance +inf.  k <= 32. */
+ * first; fewer than k rows: id -1, distance +inf.  k <= 32.
+ * Order: by the float32 key q.x - |x|^2/2, descending, then by id, ascending (equal rows: smaller id first).
+ * The distance written is max(|q|^2 - 2 key, 0) in float32 and is non-decreasing along a row; two distinct
+ * keys can round to the same distance, so equal written distances are not always in id order.
+ * An index row with a NaN or an infinite element is never returned and does not disturb the other rows; a
+ * query row with a NaN gets k times id -1, +inf, and does not disturb the other queries. */
 int nafp_search_topk_l2(const float* query, int64_t n_query, const float* index, const float* aux,
                         int64_t n_index, int dim, int k, float* out_dist, int32_t* out_ids,
                         void* workspace, int64_t workspace_bytes, void* stream);
@@ -885,7 +890,9 @@ int nafp_search_identify_check_tracks_host(const int32_t* track_first_host, int 
  * eval/utils/get_index_faiss.py:64-80 builds them; opt-in from eval_faiss.py).  Building blocks of
  * training and add (bucketing, k-means update, PQ encoding) and the two searches.  dim 64 / 128 / 256;
  * PQ: M = 64 sub-quantizers of 256 codewords (pq_centroids (M, 256, dim / M) float32), codes (n, M) uint8.
- * Ties everywhere: the smaller id (list, code, row) first.  All pointers are device pointers; results
+ * Ties everywhere: the smaller id (list, code, row) first; for nafp_ivf_flat_search a tie is a tie of the float32 key
+ * q.x - |x|^2/2, as in nafp_search_topk_l2: the distances written are non-decreasing, and two distinct keys that round to
+ * the same distance keep their key order.  All pointers are device pointers; results
  * are bit-identical from run to run and do not depend on how rows or queries are batched.
  * Status: NAFP_ERR_INVALID_ARG for a null pointer or a negative size, NAFP_ERR_UNSUPPORTED for a dim
  * outside 64 / 128 / 256, k > 32 (k1 > 128 for the wide first stage of IVFPQ-RR), nprobe > 128, M != 64, n_buckets / nlist > 16384 or an unknown lut;

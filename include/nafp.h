@@ -276,6 +276,65 @@ int nafp_ingest_i16(nafp_ingest* plan, const uint8_t* raw_bytes, int64_t raw_siz
                     int64_t n_pieces, int16_t* out, int64_t out_samples, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Varispeed: model-rate 16-bit mono PCM -> model-rate 16-bit mono PCM played `sigma` times as fast, tempo and pitch together
+ * (csrc/varispeed.hip; numpy restatement tests/_varispeed_ref.py).  Undoes the speed change of a
+ * recording before it is fingerprinted; runs after the ingest of its launch.  EXACT INTEGER ARITHMETIC: an output sample is a
+ * pure function of (the file's model-rate samples, the output index, the step), whatever shares its piece, block or launch.
+ *
+ * Step: an unsigned Q24 count of input samples per output sample, sigma = step / 2^24.  Supported: NAFP_VARISPEED_STEP_MIN <=
+ * step <= NAFP_VARISPEED_STEP_MAX (sigma 0.8 .. 1.25).  A recording played s times too fast is undone by step =
+ * round(2^24 / s); the speed reported back is 2^24 / step.
+ * Filter: Kaiser-windowed sinc, beta 8.6, 32 zero crossings a side, as the resampler's, in float64:
+ *   fc = 0.475 * min(1, 1 / sigma) cycles per input sample,  W = ceil(32 / (2 fc)) (34 for sigma <= 1, up to 43),  T = 2 W taps,
+ *   h(u) = 2 fc sinc(2 fc u) * I0(8.6 sqrt(1 - (u / W)^2)) / I0(8.6)  for |u| <= W, else 0.
+ * Table: hq[p][t] = round(2^30 h(p / 512 + W - 1 - t)) as int32, p = 0 .. 512 (513 rows: p + 1 always exists), t = 0 .. T - 1.
+ * Output n (n_in < 2^31):  P = n * step (int64),  pos = P >> 24,  frac = P & (2^24 - 1),  p = frac >> 15,  w = frac & 32767,
+ *   c_t  = (hq[p][t] * (32768 - w) + hq[p + 1][t] * w + 16384) >> 15
+ *   acc  = sum_t c_t * x[pos - W + 1 + t]      (int64; samples outside [0, n_in) are zero)
+ *   y[n] = clamp((acc + 2^29) >> 30, -32768, 32767),  arithmetic shifts;   n_out = ceil(n_in * 2^24 / step).
+ * Status: a step outside the range or n_in >= 2^31 NAFP_ERR_UNSUPPORTED, null pointers / negative sizes / an inconsistent
+ * piece NAFP_ERR_INVALID_ARG, all before any GPU call.
+ * ---------------------------------------------------------------------- */
+typedef struct nafp_varispeed nafp_varispeed;
+
+#define NAFP_VARISPEED_STEP_MIN 13421773u
+#define NAFP_VARISPEED_STEP_MAX 20971520u
+
+/* A run of consecutive output samples of one file, with the meanings of nafp_resample_piece: the model-rate samples present
+ * for it are only what its outputs need (nafp_varispeed_input_range).  56 bytes. */
+typedef struct nafp_varispeed_piece {
+    int64_t src_off;     /* int16 index in the source arena of the first sample present */
+    int64_t frame0;      /* which model-rate sample of the file that is */
+    int64_t n_frames;    /* samples present */
+    int64_t n_in;        /* model-rate samples of the whole file */
+    int64_t out0;        /* index in the file's stretched stream of the first output */
+    int64_t out_off;     /* int16 index in the output arena of that output */
+    int32_t n_out;       /* outputs */
+    int32_t reserved;
+} nafp_varispeed_piece;
+
+/* Host only. */
+int nafp_varispeed_geometry(uint32_t step, int* W, int* T);
+/* Host only: the table (513, T) int32, [phase p][tap t], as defined above. */
+int nafp_varispeed_table_host(uint32_t step, int32_t* table_host);
+int64_t nafp_varispeed_n_out(int64_t n_in, uint32_t step);                 /* -1: unsupported step / n_in outside [0, 2^31) */
+/* Host only: the samples [*first, *last) of a file of n_in samples that the outputs [n0, n1) read (first == last: none). */
+int nafp_varispeed_input_range(int64_t n0, int64_t n1, int64_t n_in, uint32_t step, int64_t* first, int64_t* last);
+/* Host only: the checks the kernel makes per piece, on a host copy of the list, before it is uploaded: indices inside
+ * src_samples / out_samples, the outputs inside the file's n_out, every sample they read present. */
+int nafp_varispeed_check_pieces_host(uint32_t step, const nafp_varispeed_piece* pieces_host, int64_t n_pieces,
+                                     int64_t src_samples, int64_t out_samples);
+/* The plan owns the device table. */
+int nafp_varispeed_create(nafp_varispeed** plan, uint32_t step);
+int nafp_varispeed_destroy(nafp_varispeed* plan);
+/* src (src_samples int16) -> out (out_samples int16) for the n_pieces pieces of pieces_dev, all device pointers.  Every index
+ * derived from a piece is checked on the device against src_samples / out_samples: an inconsistent piece is skipped, its
+ * outputs zeroed (nothing is written for one whose output range leaves the arena).  Int16 outside the pieces' output ranges
+ * is not touched. */
+int nafp_varispeed_i16(nafp_varispeed* plan, const int16_t* src, int64_t src_samples, const nafp_varispeed_piece* pieces_dev,
+                       int64_t n_pieces, int16_t* out, int64_t out_samples, void* stream);
+
+/* ------------------------------------------------------------------------
  * Block codecs in RIFF/WAVE: G.711 A-law and mu-law, IMA ADPCM and MS ADPCM at 4 bits (csrc/codec.hip, the arithmetic in
  * csrc/codec_decode.h; numpy restatement tests/_codec_ref.py).  A PRE-PASS of nafp_ingest_*, which is
  * unchanged: whole blocks are decoded to interleaved 16-bit PCM in a device arena, which nafp_ingest_i16 then reads as

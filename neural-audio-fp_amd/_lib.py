@@ -57,6 +57,14 @@ PROTOTYPES = {
     'nafp_ingest_create': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int]),
     'nafp_ingest_destroy': (c_int, [c_void_p]),
     'nafp_ingest_i16': (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p]),
+    'nafp_varispeed_geometry': (c_int, [ctypes.c_uint32, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    'nafp_varispeed_table_host': (c_int, [ctypes.c_uint32, c_void_p]),
+    'nafp_varispeed_n_out': (c_i64, [c_i64, ctypes.c_uint32]),
+    'nafp_varispeed_input_range': (c_int, [c_i64, c_i64, c_i64, ctypes.c_uint32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    'nafp_varispeed_check_pieces_host': (c_int, [ctypes.c_uint32, c_void_p, c_i64, c_i64, c_i64]),
+    'nafp_varispeed_create': (c_int, [ctypes.POINTER(c_void_p), ctypes.c_uint32]),
+    'nafp_varispeed_destroy': (c_int, [c_void_p]),
+    'nafp_varispeed_i16': (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p]),
     'nafp_codec_samples_per_block': (c_int, [c_int, c_int, c_int]),
     'nafp_codec_blocks_per_group': (c_int, [c_int, c_int, c_int]),
     'nafp_codec_decode_host': (c_int, [c_int, c_int, c_int, c_void_p, c_i64, c_void_p]),
@@ -202,6 +210,11 @@ INGEST_PIECE_DTYPE = [('raw_off', '<i8'), ('frame0', '<i8'), ('n_frames', '<i8')
                       ('out_off', '<i8'), ('n_out', '<i4'), ('channels', '<i4'), ('format', '<i4'), ('reserved', '<i4')]
 # NAFP_INGEST_* format codes (include/nafp.h): name -> (code, bytes per sample)
 INGEST_FORMATS = {'u8': (1, 1), 's16': (2, 2), 's24': (3, 3), 's32': (4, 4), 'f32': (5, 4), 'f64': (6, 8)}
+
+# nafp_varispeed_piece (include/nafp.h) as a numpy structured dtype: 56 bytes per piece
+VARISPEED_PIECE_DTYPE = [('src_off', '<i8'), ('frame0', '<i8'), ('n_frames', '<i8'), ('n_in', '<i8'), ('out0', '<i8'),
+                         ('out_off', '<i8'), ('n_out', '<i4'), ('reserved', '<i4')]
+VARISPEED_STEP_MIN, VARISPEED_STEP_MAX = 13421773, 20971520      # NAFP_VARISPEED_STEP_* (include/nafp.h): sigma 0.8 .. 1.25
 
 # nafp_codec_piece (include/nafp.h) as a numpy structured dtype: 40 bytes per piece; raw_off counts BYTES, out_off int16
 CODEC_PIECE_DTYPE = [('raw_off', '<i8'), ('n_blocks', '<i8'), ('out_off', '<i8'), ('codec', '<i4'), ('channels', '<i4'),

@@ -18,7 +18,7 @@ OBJ = os.path.join(HERE, 'build')
 LIB = os.path.join(HERE, 'libnafp.so')
 STAMP = os.path.join(HERE, '.libnafp.stamp')
 SOURCES = ['api.hip', 'melspec.hip', 'melspec_any.hip', 'conv.hip', 'conv_plan.hip', 'tail.hip', 'ntxent.hip', 'optim.hip', 'specaug.hip', 'backward.hip',
-           'search.hip', 'augment.hip', 'triplet.hip', 'norm.hip', 'ivf.hip', 'hnsw.hip', 'resample.hip', 'ingest.hip', 'codec.hip', 'flac.hip']
+           'search.hip', 'augment.hip', 'triplet.hip', 'norm.hip', 'ivf.hip', 'hnsw.hip', 'resample.hip', 'ingest.hip', 'codec.hip', 'flac.hip', 'varispeed.hip']
 HEADERS = ['nafp_common.h', 'melspec_plan.h', 'codec_decode.h', 'flac_decode.h', os.path.join('..', '..', 'include', 'nafp.h')]
 # NO PACKED-F32 INSTRUCTIONS in any kernel of the library (`-target-feature -packed-fp32-ops`, device side; the host pass prints a
 # note that it ignores the feature, filtered below).  Reason (round 6, profiles/r06_experiments.md section 5, reproducer

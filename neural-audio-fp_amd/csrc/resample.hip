@@ -46,7 +46,7 @@ static int rs_geometry(int fs_in, int fs_out, RsGeom* g) {
     return NAFP_OK;
 }
 
-static double bessel_i0(double x) {                  // sum_k ((x/2)^k / k!)^2
+double bessel_i0(double x) {                         // (varispeed.hip uses it too) sum_k ((x/2)^k / k!)^2
     const double q = 0.25 * x * x;
     double term = 1.0, sum = 1.0;
     for (int k = 1; k < 200; ++k) {

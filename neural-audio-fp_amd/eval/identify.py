@@ -9,6 +9,11 @@ overlaps its track, votes are counted.  The mapping from row to file is the `<ke
 NAFP_TRACK_TABLE=1; without it there is nothing to name a match by, and the command says so before any GPU call.
 
 The windowing (`plan_windows`) and the merge of per-window results into matches (`merge_windows`) are pure numpy.
+
+`--speeds`: a recording played a few percent fast or slow, tempo and pitch together, matches nothing as it
+is.  Each speed hypothesis fingerprints the recordings again with the speed undone on the device (`SegmentSource(step=...)`,
+nafp_varispeed_*), runs the unchanged search, matcher and merge, and `select_across_speeds` chooses among the hypotheses' matches
+per recording.  The model, the checkpoint and the index are built once; the cost is linear in the number of hypotheses.
 No rejection threshold is built in: nobody has measured one on trained weights.  Every window is reported with its score
 and votes, and `--min_score` is the user's to set.
 """
@@ -19,6 +24,74 @@ import sys
 import numpy as np
 
 MAX_SLOTS = 8192            # nafp_search_identify: k * max_len
+MAX_SPEEDS = 64             # speed hypotheses of one run
+
+
+def parse_speeds(spec):
+    """`--speeds`: a comma list of speeds (`0.96,1,1.04`) and / or ranges `lo:hi:inc` with both ends included
+    (`0.94:1.06:0.01`) -> [(step, reported speed)] in the order given, a step named twice kept once.  A speed s (the recording
+    plays s times too fast) is undone by step = round(2^24 / s) and reported back as 2^24 / step.  ValueError by name for
+    anything that is not such a list, for a speed outside 0.8 .. 1.25 and for more than MAX_SPEEDS hypotheses."""
+    from ..model.utils import varispeed as vs
+    values = []
+    for item in str(spec).split(','):
+        item = item.strip()
+        try:
+            parts = [float(v) for v in item.split(':')]
+        except ValueError:
+            raise ValueError(f'--speeds: {item!r} is not a speed or a range lo:hi:inc')
+        if not all(np.isfinite(parts)):
+            raise ValueError(f'--speeds: {item!r} is outside the supported range: every number must be finite')
+        if len(parts) == 1:
+            values.append(parts[0])
+        elif len(parts) == 3:
+            lo, hi, inc = parts
+            if not (inc > 0 and lo <= hi):
+                raise ValueError(f'--speeds: the range {item!r} needs lo <= hi and inc > 0')
+            n = (hi - lo) / inc + 1e-9                             # (a float: a tiny inc makes it huge or infinite)
+            n = MAX_SPEEDS + 1 if n > MAX_SPEEDS else int(n) + 1
+            if n > MAX_SPEEDS:
+                raise ValueError(f'--speeds: the range {item!r} holds more than {MAX_SPEEDS} hypotheses; at most {MAX_SPEEDS} are taken')
+            values += [round(lo + k * inc, 10) for k in range(n)]
+        else:
+            raise ValueError(f'--speeds: {item!r} is not a speed or a range lo:hi:inc')
+    out = []
+    for v in values:
+        if not vs.SPEED_MIN <= v <= vs.SPEED_MAX:                  # (a NaN fails the comparison too)
+            raise ValueError(f'--speeds: speed {v!r} is outside the supported range {vs.SPEED_MIN} .. {vs.SPEED_MAX}')
+        step = vs.step_for(v)
+        if step not in [st for st, _ in out]:
+            out.append((step, vs.speed_of(step)))
+    if len(out) > MAX_SPEEDS:
+        raise ValueError(f'--speeds: {len(out)} hypotheses; at most {MAX_SPEEDS} are taken')
+    return out
+
+
+def select_across_speeds(matches):
+    """The matches of every speed hypothesis (dicts with `recording`, `recording_span_s`, `score`, `speed`) -> the ones kept, per
+    recording (told apart by `_rec`, its place among the recordings, where a match carries one: a path may be given twice).  Candidates are taken by score descending, then |log speed| ascending, then speed ascending, then start of the
+    span; one is accepted unless its span overlaps an already accepted span of the same recording by more than half of the
+    shorter of the two.  Returned in the order of the recordings' first appearance, then by start of the span.  Pure host code."""
+    import math
+    which = lambda m: m.get('_rec', m['recording'])
+    order = {}
+    for m in matches:
+        order.setdefault(which(m), len(order))
+    ranked = sorted(matches, key=lambda m: (-m['score'], abs(math.log(m['speed'])), m['speed'], m['recording_span_s'][0]))
+    kept = []
+    for m in ranked:
+        a0, a1 = m['recording_span_s']
+        clash = False
+        for k in kept:
+            if which(k) != which(m):
+                continue
+            b0, b1 = k['recording_span_s']
+            if min(a1, b1) - max(a0, b0) > 0.5 * min(a1 - a0, b1 - b0):
+                clash = True
+                break
+        if not clash:
+            kept.append(m)
+    return sorted(kept, key=lambda m: (order[which(m)], m['recording_span_s'][0]))
 
 
 def plan_windows(n_segments, window, window_hop):
@@ -112,14 +185,22 @@ def load_track_tables(emb_dir, keys, shapes):
     return files, np.asarray(first, np.int32), float(hop_s), float(dur_s)
 
 
-def fingerprint_recordings(cfg, checkpoint_name, checkpoint_index, files):
-    """Fingerprints of `files` in memory: (rows (n, d) float32, rec_first (n_files + 1,)), through the path `generate` uses."""
-    from ..model.generate import StreamedEmbedder, build_fp, load_checkpoint, write_fingerprints
-    from ..model.utils.audio_utils import SegmentSource
+def load_model(cfg, checkpoint_name, checkpoint_index):
+    from ..model.generate import build_fp, load_checkpoint
     m_pre, m_fp = build_fp(cfg)
     load_checkpoint(cfg['DIR']['LOG_ROOT_DIR'] + 'checkpoint/', checkpoint_name, checkpoint_index, m_fp)
+    return m_pre, m_fp
+
+
+def fingerprint_recordings(cfg, checkpoint_name, checkpoint_index, files, step=None, model=None):
+    """Fingerprints of `files` in memory: (rows (n, d) float32, rec_first (n_files + 1,)), through the path `generate` uses.
+    step: the files are taken as played step / 2^24 times as fast (SegmentSource).  model: (m_pre, m_fp) of `load_model`, for
+    a caller that fingerprints more than once."""
+    from ..model.generate import StreamedEmbedder, write_fingerprints
+    from ..model.utils.audio_utils import SegmentSource
+    m_pre, m_fp = model or load_model(cfg, checkpoint_name, checkpoint_index)
     bsz = int(cfg['BSZ']['TS_BATCH_SZ'])
-    src = SegmentSource(files, bsz, cfg['MODEL']['DUR'], cfg['MODEL']['HOP'], cfg['MODEL']['FS'])
+    src = SegmentSource(files, bsz, cfg['MODEL']['DUR'], cfg['MODEL']['HOP'], cfg['MODEL']['FS'], step=step)
     rows = np.empty((src.n_samples, int(cfg['MODEL']['EMB_SZ'])), np.float32)
     write_fingerprints(src, StreamedEmbedder(m_pre, m_fp), rows, bsz)
     return rows, np.asarray(src.file_first, np.int64)
@@ -144,9 +225,16 @@ def match_windows(flat, index, rows, rec_first, track_first, window, window_hop,
 
 
 def identify(cfg, checkpoint_name, checkpoint_index, paths, index_type='l2', window=20, window_hop=10, k_probe=20,
-             min_overlap=4, min_votes=2, n_short=32, min_score=None, align_tol=1, output=None, emb_dir=None):
-    """`run.py identify`.  Returns the dict written to identify.json."""
+             min_overlap=4, min_votes=2, n_short=32, min_score=None, align_tol=1, output=None, emb_dir=None, speeds=None):
+    """`run.py identify`.  Returns the dict written to identify.json.  speeds: the `--speeds` text, or None -- then the command
+    prints and writes exactly what it did before the option existed."""
     from .eval_faiss import FlatL2Index, get_index, load_memmap_data
+    hypotheses = None
+    if speeds is not None:
+        try:
+            hypotheses = parse_speeds(speeds)                      # before any GPU call
+        except ValueError as e:
+            sys.exit(f'identify: {e}')
     if int(window) * int(k_probe) > MAX_SLOTS:
         sys.exit(f'identify: --window {window} x --k_probe {k_probe} = {int(window) * int(k_probe)} slots per window; the matcher '
                  f'(nafp_search_identify) takes at most {MAX_SLOTS}')
@@ -179,25 +267,42 @@ def identify(cfg, checkpoint_name, checkpoint_index, paths, index_type='l2', win
         sys.exit(f'identify: the index holds {index.ntotal} rows, its fp32 rows {flat.ntotal}')
     print(f'identify: {index.ntotal} library rows in {len(track_files)} tracks')
 
-    rows, rec_first = fingerprint_recordings(cfg, checkpoint_name, checkpoint_index, files)
-    rec, s0, ln, track, align, score, votes, overlap, n_cand = match_windows(
-        flat, index, rows, rec_first, track_first, window, window_hop, k_probe, min_overlap, min_votes, n_short)
-    matches = merge_windows(rec, s0, ln, track, align, score, votes, min_score, align_tol)
+    from ..model.utils import varispeed as vs
+    model = load_model(cfg, checkpoint_name, checkpoint_index)
+    result_matches, n_windows, best_scores = [], 0, []
+    for step, speed in hypotheses or [(vs.ONE, 1.0)]:
+        # the hypothesis "as it is" runs the path without a step: no varispeed launch
+        rows, rec_first = fingerprint_recordings(cfg, checkpoint_name, checkpoint_index, files, None if step == vs.ONE else step, model)
+        rec, s0, ln, track, align, score, votes, overlap, n_cand = match_windows(
+            flat, index, rows, rec_first, track_first, window, window_hop, k_probe, min_overlap, min_votes, n_short)
+        n_windows += int(len(rec))
+        sigma = step / vs.ONE                                      # recording seconds per stretched second
+        best = [None] * len(files)
+        for w in range(len(rec)):
+            if int(track[w]) >= 0 and np.isfinite(score[w]) and (best[int(rec[w])] is None or float(score[w]) > best[int(rec[w])]):
+                best[int(rec[w])] = float(score[w])
+        best_scores.append(best)
+        for m in merge_windows(rec, s0, ln, track, align, score, votes, min_score, align_tol):
+            tr = m['track']
+            span = [m['seg0'] * hop_s, (m['seg1'] - 1) * hop_s + dur_s]
+            row = {'_rec': m['rec'], 'recording': files[m['rec']],
+                   'recording_span_s': span if hypotheses is None else [span[0] * sigma, span[1] * sigma],
+                   'track': track_files[tr], 'track_index': tr,
+                   'track_position_s': (m['a_rec'] - int(track_first[tr])) * hop_s,
+                   'score': m['score'], 'min_votes': m['votes'], 'windows': m['windows']}
+            if hypotheses is not None:
+                row['speed'] = speed
+            result_matches.append(row)
+    if hypotheses is not None:
+        result_matches = select_across_speeds(result_matches)
 
-    result_matches = []
-    print(f'{"recording":<32s} {"from":>8s} {"to":>8s}  {"track":<32s} {"at":>9s} {"score":>7s} {"votes":>5s} {"win":>4s}')
-    for m in matches:
-        tr = m['track']
-        row = {'recording': files[m['rec']],
-               'recording_span_s': [m['seg0'] * hop_s, (m['seg1'] - 1) * hop_s + dur_s],
-               'track': track_files[tr], 'track_index': tr,
-               'track_position_s': (m['a_rec'] - int(track_first[tr])) * hop_s,
-               'score': m['score'], 'min_votes': m['votes'], 'windows': m['windows']}
-        result_matches.append(row)
+    sp_head, sp_cell = (f' {"speed":>7s}', lambda row: f' {row["speed"]:7.4f}') if hypotheses is not None else ('', lambda row: '')
+    print(f'{"recording":<32s} {"from":>8s} {"to":>8s}  {"track":<32s} {"at":>9s} {"score":>7s} {"votes":>5s} {"win":>4s}{sp_head}')
+    for row in result_matches:
         print(f'{os.path.basename(row["recording"])[-32:]:<32s} {row["recording_span_s"][0]:8.1f} {row["recording_span_s"][1]:8.1f}  '
               f'{os.path.basename(row["track"])[-32:]:<32s} {row["track_position_s"]:9.1f} {row["score"]:7.4f} {row["min_votes"]:5d} '
-              f'{row["windows"]:4d}')
-    matched = {m['rec'] for m in matches}
+              f'{row["windows"]:4d}{sp_cell(row)}')
+    matched = {row.pop('_rec') for row in result_matches}
     for r, f in enumerate(files):
         if r not in matched:
             print(f'{os.path.basename(f)[-32:]:<32s} no match')
@@ -206,7 +311,11 @@ def identify(cfg, checkpoint_name, checkpoint_index, paths, index_type='l2', win
     result = {'index_type_requested': requested, 'index_type_used': used, 'k_probe': int(k_probe), 'window': int(window),
               'window_hop': int(window_hop), 'min_overlap': int(min_overlap), 'min_votes': int(min_votes), 'n_short': int(n_short),
               'min_score': None if min_score is None else float(min_score), 'align_tol': int(align_tol), 'hop_s': hop_s,
-              'duration_s': dur_s, 'recordings': files, 'n_windows': int(len(rec)), 'matches': result_matches}
+              'duration_s': dur_s, 'recordings': files, 'n_windows': n_windows, 'matches': result_matches}
+    if hypotheses is not None:
+        # n_windows counts every hypothesis' windows; speed_best_scores[h][r]: the best window score of recording r under hypothesis h
+        result['speeds'] = [speed for _, speed in hypotheses]
+        result['speed_best_scores'] = best_scores
     out_path = output or f'{emb_dir}identify.json'
     with open(out_path, 'w') as f:
         json.dump(result, f, indent=1)

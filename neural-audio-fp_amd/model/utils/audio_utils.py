@@ -22,6 +22,7 @@ from . import codecs as cd
 from . import flac as fl
 from . import ingest as ig
 from . import resample as rs
+from . import varispeed as vs
 
 
 def n_segments(n_frames, fs=8000, duration=1., hop=.5):
@@ -319,13 +320,22 @@ class SegmentSource(FileCatalog):
     drop_the_last_non_full_batch=False)` as the generate path uses it
     (model/dataset.py:204-215): `.n_samples` segments, `len()` batches of `bsz`
     (the last one ragged), item i = segments [i*bsz, (i+1)*bsz) as int16 (n,1,T).
+
+    step (utils/varispeed, None: off): every file is taken as played step / 2^24 times as fast.  The column `n_frames` is then
+    the STRETCHED length n_out(model-rate length, step), from which the segment counts and `file_first` follow; `n_model` keeps
+    the model-rate lengths (as `files[f].n_frames` does).  The stretch exists on the device only (iter_windows).
     """
 
-    def __init__(self, fns_list, bsz, duration=1., hop=.5, fs=8000):
+    def __init__(self, fns_list, bsz, duration=1., hop=.5, fs=8000, step=None):
         super().__init__(fns_list, fs)
         self.bsz, self.duration, self.hop = int(bsz), duration, hop
         self.seg_len = int(fs * duration)
         self.hop_len = int(np.floor(hop * fs))
+        self.step = None if step is None else int(step)
+        if self.step is not None:
+            vs.geometry(self.step)                                   # ValueError by name for a step outside the range
+            self.n_model = self.n_frames
+            self.n_frames = [vs.n_out(n, self.step) for n in self.n_model]
         counts = [n_segments(nfr, fs, duration, hop) for nfr in self.n_frames]
         self.file_first = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         self.n_samples = int(self.file_first[-1])
@@ -334,6 +344,9 @@ class SegmentSource(FileCatalog):
         return (self.n_samples + self.bsz - 1) // self.bsz
 
     def _host_pcm(self, f):
+        if self.step is not None:
+            raise NotImplementedError(f'{self.fns[f]}: a speed change (step {self.step}) is undone on the device only (iter_windows + '
+                                      'StreamedEmbedder.embed_windows); there is no CPU path')
         if self.resampled[f] and self.ingest:
             raise NotImplementedError(f'{self.fns[f]}: {self.rate[f]} Hz x {self.channels[f]} x {self.format[f]} is decoded and '
                                       'resampled on the device only (iter_windows + StreamedEmbedder.embed_windows); there is no '
@@ -389,7 +402,10 @@ class SegmentSource(FileCatalog):
         the PCM every row needs is read ONCE from each file (contiguous sample range, straight into
         `arena` = alloc(n_samples), e.g. pinned memory) and row i is the window
         arena[seg_offset[i] : seg_offset[i] + seg_len] with samples >= seg_valid[i] meaning zero --
-        the same segments `iter_rows` materialises, without the 2x duplication of HOP = DUR/2."""
+        the same segments `iter_rows` materialises, without the 2x duplication of HOP = DUR/2.
+        Under a step the launch is planned in the stretched domain and the seventh item is always there (varispeed.Stage): per
+        piece the model-rate samples its stretched outputs read are planned exactly as the outputs of a launch without a step are,
+        and the stage turns them into the stretched arena that seg_offset / seg_valid index, last on the launch's stream."""
         seg_len, hop_len = self.seg_len, self.hop_len
         r = row0
         while r < row1:
@@ -405,6 +421,16 @@ class SegmentSource(FileCatalog):
                 pieces.append((f, a, b, s0, s1, total, q - r))
                 total += (s1 - s0 + 7) // 8 * 8                      # 16-B aligned piece starts
                 q += b - a
+            stretched, out_total = None, total
+            if self.step is not None:
+                # the pieces so far are stretched outputs; from here on `pieces` / `total` are the model-rate samples they read
+                stretched, pieces, total = pieces, [], 0
+                for f, a, b, s0, s1, base, o in stretched:
+                    m0, m1 = vs.input_range(s0, s1, self.n_model[f], self.step) if s1 > s0 else (0, 0)
+                    pieces.append((f, a, b, m0, m1, total, o))
+                    total += (m1 - m0 + 7) // 8 * 8
+                vs_rows = [(mp[5], mp[3], mp[4] - mp[3], self.n_model[sp[0]], sp[3], sp[5], sp[4] - sp[3], 0)
+                           for sp, mp in zip(stretched, pieces)]
             if self.resample and any(self.resampled[p[0]] for p in pieces):
                 # a launch that holds a file to convert: the arena holds the files' BYTES as they are (ingest.plan_span per piece),
                 # seg_offset / seg_valid index the model-rate arena of `total` samples that the work fills on the device; files
@@ -416,6 +442,9 @@ class SegmentSource(FileCatalog):
             else:
                 reads = [(self.fns[f], self.data_offset[f] + 2 * s0, 2 * (s1 - s0), 2 * base) for f, a, b, s0, s1, base, o in pieces]
                 used, work = total, ((None,) if self.resample else ())
+            if stretched is not None:
+                work = (vs.Stage(self.step, np.array(vs_rows, dtype=vs.PIECE_DTYPE), out_total, work[0] if work else None),)
+                pieces = stretched
             arena = alloc(used) if alloc is not None else np.empty(max(used, 1), np.int16)
             raw = arena.view(np.uint8)
             for fn, file_off, n_bytes, at in reads:

@@ -1,6 +1,6 @@
 """Kernel cost of the general ingest (NAFP_INGEST_ANY=1, csrc/ingest.hip) for one generate launch of 640 segments.
 
-    python tools/ingest_bench.py [reps=7] [launches_per_rep=20]
+    python tools/ingest_bench.py [reps=7] [launches_per_rep=20] [--varispeed]
 
 Device-event times, every shape warmed up first, `reps` windows of `launches_per_rep` launches each per case, the cases
 alternating inside a rep so that drift hits them alike; median and range over the reps, per launch:
@@ -18,6 +18,9 @@ alternating inside a rep so that drift hits them alike; median and range over th
      ingest of the PCM it decoded and the log-mel kernel; `prepass_all_failed` is the same launch with every record cut to 8
      bytes, i.e. the launch overhead, the allocations and the store stage's zero fill without the serial stage; `index` is the
      host's one pass over the file (nafp_flac_index_host), in MB/s.
+  5. the varispeed pass (`identify --speeds`, csrc/varispeed.hip) at sigma = 1 / 1.04 and 1 / 0.96 over the launch's 640 stretched
+     segments, next to the ingest it follows (16-bit stereo at 44.1 kHz, the model-rate samples the stretched outputs read) and the
+     log-mel kernel of the same launch.  `--varispeed` runs this row alone.
 A launch is 640 one-second segments at a hop of 0.5 s: 320.5 s of audio, cut into 30-s files as generate would (11 pieces).
 One JSON line at the end."""
 import json
@@ -95,6 +98,55 @@ def flac_launch(ig, fl, index, fs_in, fs_out, file_bytes):
     return np.concatenate(f_rows), np.array(i_rows, dtype=ig.PIECE_DTYPE), raw, scratch, out_pos
 
 
+def varispeed_launch(vs, ig, step, fs_in, ch, code, width):
+    """The launch of recordings under a step as SegmentSource.iter_windows cuts it: per 30-s file the stretched outputs, the
+    model-rate samples they read, and the file's frames those need.  -> (varispeed pieces, ingest pieces, raw bytes, model-rate
+    samples, outputs)."""
+    total_out = (SEGMENTS - 1) * 4000 + 8000
+    n_model, n_file = FILE_SECONDS * 8000, FILE_SECONDS * fs_in
+    v_rows, i_rows, raw_pos, mid_pos, out_pos = [], [], 0, 0, 0
+    while out_pos < total_out:
+        n_out = min(vs.n_out(n_model, step), total_out - out_pos)
+        m0, m1 = vs.input_range(0, n_out, n_model, step)
+        first, last = ig.input_range(m0, m1, n_file, fs_in, 8000)
+        i_rows.append((raw_pos, first, last - first, n_file, m0, mid_pos, m1 - m0, ch, code, 0))
+        v_rows.append((mid_pos, m0, m1 - m0, n_model, 0, out_pos, n_out, 0))
+        raw_pos += ((last - first) * ch * width + 15) // 16 * 16
+        mid_pos += (m1 - m0 + 7) // 8 * 8
+        out_pos += (n_out + 7) // 8 * 8
+    return np.array(v_rows, dtype=vs.PIECE_DTYPE), np.array(i_rows, dtype=ig.PIECE_DTYPE), raw_pos, mid_pos, out_pos
+
+
+def varispeed_rows(res, rng):
+    """5. the varispeed pass next to the ingest it follows and the log-mel of the same launch."""
+    from neural_audio_fp_amd import _lib
+    from neural_audio_fp_amd.model.utils import ingest as ig
+    from neural_audio_fp_amd.model.utils import varispeed as vs
+    lib, st = _lib.load(), _lib.current_stream()
+    code, width = _lib.INGEST_FORMATS['s16']
+    for name, speed in (('varispeed_1.04', 1.04), ('varispeed_0.96', 0.96)):
+        step = vs.step_for(speed)
+        v_p, i_p, raw_bytes, n_mid, n_out = varispeed_launch(vs, ig, step, 44100, 2, code, width)
+        raw = torch.from_numpy(rng.integers(-32768, 32768, size=raw_bytes // 2).astype(np.int16)).cuda().view(torch.uint8)
+        mid = torch.zeros((n_mid,), dtype=torch.int16, device='cuda')
+        out = torch.zeros((n_out,), dtype=torch.int16, device='cuda')
+        ig.check_pieces(44100, 8000, i_p, raw_bytes, n_mid)
+        vs.check_pieces(step, v_p, n_mid, n_out)
+        d_i = torch.from_numpy(i_p.view(np.uint8).reshape(-1)).cuda()
+        d_v = torch.from_numpy(v_p.view(np.uint8).reshape(-1)).cuda()
+        p_ing, p_vs = ig.plan_for(44100, 8000), vs.plan_for(step)
+        f_ing = lambda: _lib.check(lib.nafp_ingest_i16(p_ing.handle, _lib.ptr(raw), raw_bytes, _lib.ptr(d_i), len(i_p), _lib.ptr(mid), n_mid,
+                                                       st), 'ingest_i16')
+        f_vs = lambda: _lib.check(lib.nafp_varispeed_i16(p_vs.handle, _lib.ptr(mid), n_mid, _lib.ptr(d_v), len(v_p), _lib.ptr(out), n_out, st),
+                                  'varispeed_i16')
+        f_ing()
+        mel = mel_for(8000, out, n_out)
+        t = timed([f_ing, f_vs, mel])
+        res[name] = {'step': step, 'sigma': step / vs.ONE, 'pieces': len(v_p), 'model_rate_samples': int(n_mid), 'outputs': int(n_out),
+                     'taps_per_output': p_vs.T, 'ingest_s16x2_44100': t[0], 'varispeed': t[1], 'log_mel': t[2],
+                     'varispeed_over_ingest': round(t[1]['median_ms'] / t[0]['median_ms'], 3)}
+
+
 def timed(fns):
     """Per-launch milliseconds of each callable: median and (min, max) over REPS windows of PER_REP launches, alternating."""
     for fn in fns:
@@ -132,6 +184,10 @@ def main():
     from neural_audio_fp_amd import _lib
     res = {'device': torch.cuda.get_device_name(0), 'segments': SEGMENTS, 'reps': REPS, 'launches_per_rep': PER_REP}
     rng = np.random.default_rng(7)
+    if '--varispeed' in sys.argv:
+        varispeed_rows(res, rng)
+        print(json.dumps(res))
+        return
 
     # 1. 16-bit stereo 44.1 kHz: both kernels on the same samples
     p_new, raw_bytes, n_out = pieces_for(ig, 44100, 8000, 4, 1, (2, _lib.INGEST_FORMATS['s16'][0], 0))
@@ -246,6 +302,7 @@ def main():
                      'index': {'seconds': round(t_index, 4), 'mb_per_s': round(len(data) / 1e6 / t_index, 1), 'frames': len(index)},
                      'prepass': t[0], 'prepass_all_failed': t[1], 'ingest': t[2], 'log_mel': t[3],
                      'prepass_over_ingest': round(t[0]['median_ms'] / t[2]['median_ms'], 3)}
+    varispeed_rows(res, rng)
     print(json.dumps(res))
 
 

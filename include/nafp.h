@@ -944,6 +944,42 @@ int nafp_search_identify(const float* query, int64_t n_query, const float* index
                          int32_t* out_votes, int32_t* out_overlap, int32_t* out_n_cand, void* stream);
 int nafp_search_identify_check_tracks_host(const int32_t* track_first_host, int n_tracks, int64_t n_index);
 
+/* Identification under tempo hypotheses: nafp_search_identify along slanted lines, for a recording that was time-stretched
+ * (tempo changed, pitch kept).  Under a tempo ratio rho, query segment i of a window falls on library row a + round(i * rho),
+ * not a + i; every hypothesis is matched in this one launch on the same fingerprints.  The arguments are those of
+ * nafp_search_identify plus rho_host (n_rho values, a HOST pointer: they travel in the kernel arguments) and out_rho.
+ *   - hypothesis r < n_rho is rho_host[r], 16.16 fixed point, the library rows advanced per query segment;
+ *     off_r(i) = (i * rho_host[r] + 32768) >> 16 (i < 8192, rho <= 81920: 32 bits hold it), non-decreasing in i;
+ *   - len_t as in nafp_search_identify;
+ *   - candidates: every slot (i < len_t, j < k) with id = topk_ids[task_q0[t] + i, j] in [0, n_index) gives, for EVERY r, the
+ *     triple (tr, r, a): tr the track of id, a = id - off_r(i) (any sign).  A candidate is a DISTINCT triple; its votes are
+ *     the number of slots that gave it;
+ *   - overlap: i0 = the smallest i with a + off_r(i) >= first[tr], i1 = the smallest i with a + off_r(i) >= first[tr + 1],
+ *     both clipped to [0, len_t], the track clipped to [0, n_index); n_ov = i1 - i0.  A candidate with
+ *     n_ov < min(min_overlap, len_t), n_ov == 0 or votes < min_votes is dropped;
+ *   - shortlist: the n_short best of the rest by votes descending, then tr, r, a ascending; out_n_cand[t] (or NULL) counts
+ *     the rest BEFORE this cut;
+ *   - score of a shortlisted candidate = mean_{i0 <= i < i1} query[task_q0[t] + i] . index[a + off_r(i)], in the one summation
+ *     order of the sequence score: the bits of nafp_search_seq_scores on the rows index[a + off_r(i)] gathered into an array
+ *     of their own.  A NaN or -inf score drops the candidate;
+ *   - out_track / out_align / out_score / out_votes / out_overlap / out_rho (n_tasks, n_out): the n_out best by score
+ *     descending, then tr, r, a ascending (of two hypotheses that give the same rows, the one first in rho_host); padding
+ *     track -1, align 0, rho -1, score -inf, votes 0, overlap 0.  out_rho holds r, the place in rho_host;
+ *   - every index row read lies inside its track and inside [0, n_index), whatever topk_ids or track_first hold;
+ *   - bit-identical from run to run; a task's rows do not depend on what else is in the launch;
+ *   - with rho_host = {65536} every array equals nafp_search_identify's byte for byte (out_rho 0, padding -1).
+ * Status, before any GPU call: NAFP_ERR_INVALID_ARG for a null pointer (out_n_cand excepted) or a negative size;
+ * NAFP_ERR_UNSUPPORTED for n_rho outside 1..16, a rho outside 52429..81920 (0.8 .. 1.25), k * max_len * n_rho > 8192 and
+ * every limit of nafp_search_identify; n_tasks == 0 returns NAFP_OK without a launch. */
+int nafp_search_identify_tempo(const float* query, int64_t n_query, const float* index, int64_t n_index, int dim,
+                               const int32_t* topk_ids, int k,
+                               const int32_t* task_q0, const int32_t* task_len, int64_t n_tasks, int max_len,
+                               const int32_t* track_first, int n_tracks,
+                               const int32_t* rho_host, int n_rho,
+                               int min_overlap, int min_votes, int n_short, int n_out,
+                               int32_t* out_track, int32_t* out_align, float* out_score,
+                               int32_t* out_votes, int32_t* out_overlap, int32_t* out_n_cand, int32_t* out_rho, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Approximate indexes: IVF-Flat and IVF-PQ (faiss IndexIVFFlat / IndexIVFPQ as
  * eval/utils/get_index_faiss.py:64-80 builds them; opt-in from eval_faiss.py).  Building blocks of

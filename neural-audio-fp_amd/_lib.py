@@ -136,6 +136,9 @@ PROTOTYPES = {
                                      c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p]),
     'nafp_search_identify_check_tracks_host': (c_int, [c_void_p, c_int, c_i64]),
+    'nafp_search_identify_tempo': (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_i64, c_int,
+                                           c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'nafp_ivf_bucket_workspace_bytes': (c_i64, [c_i64, c_int, c_int]),
     'nafp_ivf_bucket': (c_int, [c_void_p, c_int, c_i64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
     'nafp_ivf_kmeans_update': (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),

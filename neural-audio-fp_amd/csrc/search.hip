@@ -20,6 +20,7 @@
 //   search_seq_score_kernel<D> mean_i q[t+i] . x[c+i] for candidate sequence starts c (eval_faiss.py:221-230)
 //   search_seq_match_kernel<D> top-k ids -> offset-compensated unique candidates -> scores -> the n_out best (eval_faiss.py:213-232)
 //   search_identify_kernel<D>  top-k ids -> (track, alignment) candidates with votes -> overlap-only scores -> the n_out best (eval/identify.py)
+//   search_identify_tempo_kernel<D>  the same along slanted lines: (track, tempo hypothesis, alignment) candidates (identify --tempos)
 #include "nafp_common.h"
 
 #include <algorithm>
@@ -625,6 +626,199 @@ __global__ __launch_bounds__(256) void search_identify_kernel(
     }
 }
 
+// Identification under tempo hypotheses: search_identify_kernel along slanted lines (include/nafp.h,
+// nafp_search_identify_tempo, states the contract).  Hypothesis r advances off_r(i) = (i * rho[r] + 32768) >> 16 library rows in
+// i query segments, so slot (i, j) gives one key per r: track << 36 | r << 32 | (a + IDENT_BIAS), a = topk[q0 + i, j] - off_r(i)
+// (off_r(8191) <= 10239 at rho = 81920: the bias of 2^14 still covers it).  The seven steps and the 12 P bytes of LDS are those of
+// search_identify_kernel with P the power of two that holds k * len * n_rho slots; what differs:
+//   1. gather    one binary search of track_first per slot, then n_rho keys; the keys of hypothesis r lie at [r * k * len, ..)
+//   4. filter    i0 / i1 = the first segment whose row a + off_r(i) reaches the track's first row / the next track's: two binary
+//                searches over i (off_r is non-decreasing); the rows of [i0, i1) then lie in the track and in [0, N)
+//   6. score     seq_score_wave's order over the rows a + off_r(i): the bits of nafp_search_seq_scores on the gathered rows
+// The sorted key order is (track, r, a): it breaks the ties of the shortlist and of the ranking as the contract says.
+// The hypotheses come by value in the kernel arguments and are copied to LDS once (a lane-dependent index into an argument
+// would be a scratch copy per lane).
+constexpr int IDENT_MAX_RHO = 16;
+constexpr int IDENT_RHO_MIN = 52429, IDENT_RHO_MAX = 81920;      // 0.8 .. 1.25 in 16.16
+struct IdentRho { int v[IDENT_MAX_RHO]; };
+
+__device__ __forceinline__ int ident_off(int i, int rho) { return (i * rho + 32768) >> 16; }      // i < 8192: below 2^30
+
+// the smallest i in [0, len] with a + off(i) >= bound, len if there is none
+__device__ __forceinline__ int ident_first_at(int a, int rho, int len, int64_t bound) {
+    int lo = 0, hi = len;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((int64_t)a + ident_off(mid, rho) >= bound) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ void ident_overlap_tempo(const int* __restrict__ first, int64_t N, int tr, int a, int rho, int len,
+                                                    int* i0, int* i1) {
+    const int64_t lo = std::max<int64_t>(first[tr], 0), hi = std::min<int64_t>(first[tr + 1], N);
+    *i0 = ident_first_at(a, rho, len, lo);
+    *i1 = std::max(*i0, ident_first_at(a, rho, len, hi));
+}
+
+// mean_{i0 <= i < i1} Q[q0 + i] . X[a + off(i)] by one wave, in the order of seq_score_wave
+template <int D>
+__device__ __forceinline__ float seq_score_wave_tempo(const float* __restrict__ Q, const float* __restrict__ X, int q0, int a,
+                                                      int rho, int i0, int i1, int lane) {
+    float s = 0.f;
+    for (int i = i0; i < i1; ++i) {
+        const float* qp = Q + (int64_t)(q0 + i) * D; const float* xp = X + ((int64_t)a + ident_off(i, rho)) * D;
+        for (int e = lane; e < D; e += 64) s = fmaf(qp[e], xp[e], s);
+    }
+    s = wave_sum(s);
+    return s / (float)(i1 - i0);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void search_identify_tempo_kernel(
+        const float* __restrict__ Q, int n_query, const float* __restrict__ X, int64_t N, const int* __restrict__ topk, int k,
+        const int* __restrict__ task_q0, const int* __restrict__ task_len, int max_len, const int* __restrict__ first, int n_tracks,
+        IdentRho rho, int n_rho, int min_overlap, int min_votes, int n_short, int n_out, int* __restrict__ out_track,
+        int* __restrict__ out_align, float* __restrict__ out_score, int* __restrict__ out_votes, int* __restrict__ out_overlap,
+        int* __restrict__ out_n_cand, int* __restrict__ out_rho, int p_max) {
+    extern __shared__ unsigned long long ident_keys[];           // [p_max] keys, then [p_max] unsigned
+    unsigned* aux = (unsigned*)(ident_keys + p_max);
+    __shared__ unsigned long long sl_key[IDENT_MAX_SHORT];
+    __shared__ unsigned sl_su[IDENT_MAX_SHORT];                  // the score as an ordered unsigned; 0: dropped
+    __shared__ float sl_score[IDENT_MAX_SHORT];
+    __shared__ int sl_votes[IDENT_MAX_SHORT], sl_ov[IDENT_MAX_SHORT];
+    __shared__ int wcnt[4], wval[4], rho_s[IDENT_MAX_RHO];
+    const int task = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (tid < IDENT_MAX_RHO) {
+        int v = 0;
+#pragma unroll
+        for (int r = 0; r < IDENT_MAX_RHO; ++r) v = tid == r ? rho.v[r] : v;
+        rho_s[tid] = v;
+    }
+    const int q0 = task_q0[task];
+    int len = 0;
+    if (q0 >= 0 && q0 < n_query) len = std::max(0, std::min(std::min(task_len[task], max_len), n_query - q0));
+    const int S0 = k * len, S = S0 * n_rho;                        // <= k * max_len * n_rho <= p_max
+    int P = 1;
+    while (P < S) P <<= 1;
+    __syncthreads();
+
+    // 1. gather
+    for (int s = tid; s < S0; s += 256) {
+        const int i = s / k;
+        const int id = topk[(int64_t)(q0 + i) * k + (s - i * k)];
+        const bool present = id >= 0 && id < N;
+        int lo = 0, hi = n_tracks - 1;                             // the last track whose first row is <= id
+        while (present && lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (first[mid] <= id) lo = mid; else hi = mid - 1;
+        }
+        for (int r = 0; r < n_rho; ++r)
+            ident_keys[r * S0 + s] = !present ? IDENT_NONE
+                : ((unsigned long long)(unsigned)lo << 36) | ((unsigned long long)r << 32) | (unsigned)(id - ident_off(i, rho_s[r]) + IDENT_BIAS);
+    }
+    for (int s = S + tid; s < P; s += 256) ident_keys[s] = IDENT_NONE;
+    __syncthreads();
+    // 2. sort
+    bitonic_sort_lds(ident_keys, P, tid);
+    // 3. compact the run heads and their positions, 256 slots at a time (as search_identify_kernel does)
+    int n_uniq = 0, n_valid = 0;
+    for (int base = 0; base < P; base += 256) {
+        const int i = base + tid;
+        unsigned long long c = IDENT_NONE;
+        bool head = false;
+        if (i < P) { c = ident_keys[i]; head = c != IDENT_NONE && (i == 0 || ident_keys[i - 1] != c); }
+        const unsigned long long m = __ballot(head), mv = __ballot(c != IDENT_NONE);
+        if (lane == 0) { wcnt[wave] = __popcll(m); wval[wave] = __popcll(mv); }
+        __syncthreads();
+        int before = n_uniq;
+        for (int w = 0; w < wave; ++w) before += wcnt[w];
+        if (head) {
+            const int pos = before + __popcll(m & ((1ull << lane) - 1ull));
+            ident_keys[pos] = c;
+            aux[pos] = (unsigned)i;
+        }
+        n_uniq += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        n_valid += wval[0] + wval[1] + wval[2] + wval[3];
+        __syncthreads();
+    }
+    // 4. votes, overlap, the two minima -> selection keys in place of the positions
+    int P2 = 1;
+    while (P2 < n_uniq) P2 <<= 1;                                  // <= P: n_uniq <= S
+    const int need_ov = std::min(min_overlap, len);
+    int n_cand = 0;
+    for (int base = 0; base < P2; base += 256) {
+        const int n = base + tid;
+        unsigned sel = 0xffffffffu;
+        if (n < n_uniq) {
+            const int v = (int)(n + 1 < n_uniq ? aux[n + 1] : (unsigned)n_valid) - (int)aux[n];
+            const unsigned long long key = ident_keys[n];
+            int i0, i1;
+            ident_overlap_tempo(first, N, (int)(key >> 36), (int)(unsigned)key - IDENT_BIAS, rho_s[(key >> 32) & 15u], len, &i0, &i1);
+            if (i1 - i0 >= need_ov && i1 > i0 && v >= min_votes) sel = ((unsigned)(IDENT_MAX_SLOTS - v) << 13) | (unsigned)n;
+        }
+        const unsigned long long m = __ballot(sel != 0xffffffffu);
+        if (lane == 0) wcnt[wave] = __popcll(m);
+        __syncthreads();                                           // every aux[n + 1] of this pass is read
+        if (n < P2) aux[n] = sel;
+        n_cand += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        __syncthreads();
+    }
+    if (tid == 0 && out_n_cand) out_n_cand[task] = n_cand;
+    // 5. shortlist
+    bitonic_sort_lds(aux, P2, tid);
+    const int n_sl = std::min(n_short, n_cand);
+    // 6. score each shortlisted candidate once, over its overlap
+    for (int m = wave; m < n_sl; m += 4) {
+        const unsigned sel = aux[m];
+        const unsigned long long key = ident_keys[sel & 8191u];
+        const int a = (int)(unsigned)key - IDENT_BIAS, rh = rho_s[(key >> 32) & 15u];
+        int i0, i1;
+        ident_overlap_tempo(first, N, (int)(key >> 36), a, rh, len, &i0, &i1);
+        const float sc = seq_score_wave_tempo<D>(Q, X, q0, a, rh, i0, i1, lane);
+        if (lane == 0) {
+            const bool keep = !(sc != sc) && sc != -INFINITY;
+            unsigned u = __float_as_uint(sc == 0.f ? 0.f : sc);       // -0 ranks with +0
+            u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;
+            sl_key[m] = key; sl_su[m] = keep ? u : 0u; sl_score[m] = sc;
+            sl_votes[m] = IDENT_MAX_SLOTS - (int)(sel >> 13); sl_ov[m] = i1 - i0;
+        }
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    // 7. n_out rounds of arg-max: score descending, then (track, r, a) ascending.  The keys are distinct, so the order is total.
+    unsigned long long prev_su = 1ull << 32, prev_key = 0ull;      // above every candidate
+    for (int r = 0; r < n_out; ++r) {
+        unsigned long long b_su = 0ull, b_key = IDENT_NONE;
+        int b_m = -1;
+        for (int m = lane; m < n_sl; m += 64) {
+            const unsigned long long su = sl_su[m], key = sl_key[m];
+            const bool below = su < prev_su || (su == prev_su && key > prev_key);
+            const bool better = su > b_su || (su == b_su && key < b_key);
+            if (su != 0ull && below && better) { b_su = su; b_key = key; b_m = m; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long o_su = __shfl_xor(b_su, o, 64), o_key = __shfl_xor(b_key, o, 64);
+            const int o_m = __shfl_xor(b_m, o, 64);
+            if (o_su > b_su || (o_su == b_su && o_key < b_key)) { b_su = o_su; b_key = o_key; b_m = o_m; }
+        }
+        if (lane == 0) {
+            const int64_t o = (int64_t)task * n_out + r;
+            const bool got = b_m >= 0;
+            out_track[o] = got ? (int)(b_key >> 36) : -1;
+            out_align[o] = got ? (int)(unsigned)b_key - IDENT_BIAS : 0;
+            out_rho[o] = got ? (int)((b_key >> 32) & 15u) : -1;
+            out_score[o] = got ? sl_score[b_m] : -INFINITY;
+            out_votes[o] = got ? sl_votes[b_m] : 0;
+            out_overlap[o] = got ? sl_ov[b_m] : 0;
+        }
+        if (b_m < 0) { prev_su = 0ull; prev_key = IDENT_NONE; }   // the candidates ran out: the later rounds find nothing
+        else { prev_su = b_su; prev_key = b_key; }
+    }
+}
+
 template <int D, int K>
 static int launch_topk(const float* Q, int nq, const float* X, const float* hn, int64_t N, float* pk, int* pi, int splits,
                        int tps, hipStream_t st) {
@@ -784,6 +978,47 @@ extern "C" int nafp_search_identify(const float* query, int64_t n_query, const f
     else if (dim == 256) NAFP_IDENT(256)
     else NAFP_IDENT(64)
 #undef NAFP_IDENT
+    NAFP_LAUNCH_CHECK();
+    return NAFP_OK;
+}
+
+extern "C" int nafp_search_identify_tempo(const float* query, int64_t n_query, const float* index, int64_t n_index, int dim,
+                                          const int32_t* topk_ids, int k, const int32_t* task_q0, const int32_t* task_len,
+                                          int64_t n_tasks, int max_len, const int32_t* track_first, int n_tracks,
+                                          const int32_t* rho_host, int n_rho, int min_overlap, int min_votes, int n_short,
+                                          int n_out, int32_t* out_track, int32_t* out_align, float* out_score, int32_t* out_votes,
+                                          int32_t* out_overlap, int32_t* out_n_cand, int32_t* out_rho, void* stream) {
+    if (!query || !index || !topk_ids || !task_q0 || !task_len || !track_first || !rho_host || !out_track || !out_align ||
+        !out_score || !out_votes || !out_overlap || !out_rho || n_query < 0 || n_index < 0 || n_tasks < 0)
+        return NAFP_ERR_INVALID_ARG;
+    if (dim != 64 && dim != 128 && dim != 256) return NAFP_ERR_UNSUPPORTED;
+    if (n_rho < 1 || n_rho > IDENT_MAX_RHO) return NAFP_ERR_UNSUPPORTED;
+    if (k < 1 || k > 32 || max_len < 1 || k * (int64_t)max_len * n_rho > IDENT_MAX_SLOTS) return NAFP_ERR_UNSUPPORTED;
+    if (n_short < 1 || n_short > IDENT_MAX_SHORT || n_out < 1 || n_out > 32 || n_out > n_short) return NAFP_ERR_UNSUPPORTED;
+    if (min_overlap < 1 || min_votes < 1 || n_tracks < 1 || n_tracks > (1 << 24)) return NAFP_ERR_UNSUPPORTED;
+    if (n_index > ((int64_t)1 << 31) - IDENT_BIAS || n_query >= ((int64_t)1 << 31) || n_tasks >= ((int64_t)1 << 31)) return NAFP_ERR_UNSUPPORTED;
+    IdentRho rho = {};
+    for (int r = 0; r < n_rho; ++r) {
+        if (rho_host[r] < IDENT_RHO_MIN || rho_host[r] > IDENT_RHO_MAX) return NAFP_ERR_UNSUPPORTED;
+        rho.v[r] = rho_host[r];
+    }
+    if (n_tasks == 0) return NAFP_OK;
+    int p_max = 1;
+    while (p_max < k * max_len * n_rho) p_max <<= 1;
+    const int lds = p_max * 12;
+    hipStream_t st = (hipStream_t)stream;
+#define NAFP_IDENT_TEMPO(D_)                                                                                                    \
+    {                                                                                                                           \
+        if (lds > 48 * 1024)                                                                                                    \
+            NAFP_HIP_CHECK(hipFuncSetAttribute((const void*)search_identify_tempo_kernel<D_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); \
+        search_identify_tempo_kernel<D_><<<(unsigned)n_tasks, 256, lds, st>>>(query, (int)n_query, index, n_index, topk_ids, k,  \
+            task_q0, task_len, max_len, track_first, n_tracks, rho, n_rho, min_overlap, min_votes, n_short, n_out, out_track,    \
+            out_align, out_score, out_votes, out_overlap, out_n_cand, out_rho, p_max);                                          \
+    }
+    if (dim == 128) NAFP_IDENT_TEMPO(128)
+    else if (dim == 256) NAFP_IDENT_TEMPO(256)
+    else NAFP_IDENT_TEMPO(64)
+#undef NAFP_IDENT_TEMPO
     NAFP_LAUNCH_CHECK();
     return NAFP_OK;
 }

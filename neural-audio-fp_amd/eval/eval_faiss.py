@@ -194,6 +194,42 @@ class FlatL2Index:
                                                       _lib.ptr(n_cand), _lib.current_stream()), 'search_identify')
         return track, align, score, votes, overlap, n_cand
 
+    def identify_tempo(self, q, topk_ids, task_q0, task_len, track_first, rhos, n_out=1, n_short=32, min_overlap=4, min_votes=2,
+                       max_len=None):
+        """`identify` under tempo hypotheses, all in one launch (nafp_search_identify_tempo, include/nafp.h): `rhos` (1 .. 16 ints
+        on the host, 16.16 fixed point within 52429 .. 81920) are the library rows advanced per query segment; segment i of a window
+        at alignment a falls on row a + ((i * rho + 32768) >> 16).  The other arguments are those of `identify`.  Returns `identify`'s
+        tuple with one more member: (track, align, score, votes, overlap) (T, n_out), n_cand (T,) and rho (T, n_out), the place in
+        `rhos` of each result's hypothesis (padding -1)."""
+        q = _lib.require_cuda(q, 'q')
+        first = np.ascontiguousarray(track_first.numpy() if torch.is_tensor(track_first) else track_first)
+        if first.dtype != np.int32 or first.ndim != 1 or first.shape[0] < 2:
+            raise TypeError('identify_tempo: track_first (n_tracks + 1,) int32 on the host')
+        rho = np.ascontiguousarray(np.asarray(rhos, dtype=np.int64).reshape(-1).astype(np.int32))
+        n_tracks = int(first.shape[0]) - 1
+        _lib.check(self._lib.nafp_search_identify_check_tracks_host(first.ctypes.data, n_tracks, self.ntotal), 'search_identify_tempo (track_first)')
+        T = int(task_q0.shape[0])
+        if q.dtype != torch.float32 or topk_ids.dtype != torch.int32 or task_q0.dtype != torch.int32 or task_len.dtype != torch.int32:
+            raise TypeError('identify_tempo: q float32, topk_ids / task_q0 / task_len int32')
+        if q.dim() != 2 or q.shape[1] != self.d or topk_ids.dim() != 2 or topk_ids.shape[0] != q.shape[0] or task_len.shape[0] != T:
+            raise ValueError('identify_tempo: q (nq, d), topk_ids (nq, k), task_q0 and task_len (T,)')
+        if max_len is None:
+            max_len = max(int(task_len.max()), 1) if T else 1
+        n_out = int(n_out)
+        track, align, votes, overlap, rho_out = (torch.empty((T, n_out), dtype=torch.int32, device=self.device) for _ in range(5))
+        score = torch.empty((T, n_out), dtype=torch.float32, device=self.device)
+        n_cand = torch.empty((T,), dtype=torch.int32, device=self.device)
+        q, topk_ids, task_q0, task_len = q.contiguous(), topk_ids.contiguous(), task_q0.contiguous(), task_len.contiguous()
+        first_dev = torch.from_numpy(first).to(self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.nafp_search_identify_tempo(_lib.ptr(q), q.shape[0], _lib.ptr(self._x), self.ntotal, self.d, _lib.ptr(topk_ids),
+                                                            int(topk_ids.shape[1]), _lib.ptr(task_q0), _lib.ptr(task_len), T, int(max_len),
+                                                            _lib.ptr(first_dev), n_tracks, rho.ctypes.data, int(rho.shape[0]),
+                                                            int(min_overlap), int(min_votes), int(n_short), n_out, _lib.ptr(track),
+                                                            _lib.ptr(align), _lib.ptr(score), _lib.ptr(votes), _lib.ptr(overlap),
+                                                            _lib.ptr(n_cand), _lib.ptr(rho_out), _lib.current_stream()), 'search_identify_tempo')
+        return track, align, score, votes, overlap, n_cand, rho_out
+
 
 def seq_match_enabled():
     """NAFP_SEQ_MATCH=1: the evaluation ranks the sequence candidates on the device (`FlatL2Index.sequence_match`) instead of on

@@ -14,6 +14,10 @@ The windowing (`plan_windows`) and the merge of per-window results into matches 
 is.  Each speed hypothesis fingerprints the recordings again with the speed undone on the device (`SegmentSource(step=...)`,
 nafp_varispeed_*), runs the unchanged search, matcher and merge, and `select_across_speeds` chooses among the hypotheses' matches
 per recording.  The model, the checkpoint and the index are built once; the cost is linear in the number of hypotheses.
+`--tempos`: a time-stretched recording (tempo changed, pitch kept) is found by the segment search as it is,
+but segment i of a window falls on library row a + round(i * tempo), not a + i.  All tempo hypotheses are matched in ONE launch of
+`FlatL2Index.identify_tempo` (nafp_search_identify_tempo) on the fingerprints already computed; `merge_windows(..., rho=)` follows the
+slanted lines from window to window.  With `--speeds p` in front, a pitch shift by p becomes a tempo of 1 / p.
 No rejection threshold is built in: nobody has measured one on trained weights.  Every window is reported with its score
 and votes, and `--min_score` is the user's to set.
 """
@@ -25,6 +29,38 @@ import numpy as np
 
 MAX_SLOTS = 8192            # nafp_search_identify: k * max_len
 MAX_SPEEDS = 64             # speed hypotheses of one run
+MAX_TEMPOS = 16             # nafp_search_identify_tempo: hypotheses of one launch
+TEMPO_ONE = 1 << 16         # a tempo hypothesis is 16.16 fixed point
+TEMPO_MIN, TEMPO_MAX = 0.8, 1.25
+MAX_SHORT = 256             # n_short of either matcher
+
+
+def _grid(spec, opt, what, limit):
+    """A comma list of values and / or ranges `lo:hi:inc` with both ends included -> the floats in the order given.  ValueError
+    naming the option `opt` for anything that is not such a list, and for a range of more than `limit` values."""
+    values = []
+    for item in str(spec).split(','):
+        item = item.strip()
+        try:
+            parts = [float(v) for v in item.split(':')]
+        except ValueError:
+            raise ValueError(f'{opt}: {item!r} is not a {what} or a range lo:hi:inc')
+        if not all(np.isfinite(parts)):
+            raise ValueError(f'{opt}: {item!r} is outside the supported range: every number must be finite')
+        if len(parts) == 1:
+            values.append(parts[0])
+        elif len(parts) == 3:
+            lo, hi, inc = parts
+            if not (inc > 0 and lo <= hi):
+                raise ValueError(f'{opt}: the range {item!r} needs lo <= hi and inc > 0')
+            n = (hi - lo) / inc + 1e-9                             # (a float: a tiny inc makes it huge or infinite)
+            n = limit + 1 if n > limit else int(n) + 1
+            if n > limit:
+                raise ValueError(f'{opt}: the range {item!r} holds more than {limit} hypotheses; at most {limit} are taken')
+            values += [round(lo + k * inc, 10) for k in range(n)]
+        else:
+            raise ValueError(f'{opt}: {item!r} is not a {what} or a range lo:hi:inc')
+    return values
 
 
 def parse_speeds(spec):
@@ -33,30 +69,8 @@ def parse_speeds(spec):
     plays s times too fast) is undone by step = round(2^24 / s) and reported back as 2^24 / step.  ValueError by name for
     anything that is not such a list, for a speed outside 0.8 .. 1.25 and for more than MAX_SPEEDS hypotheses."""
     from ..model.utils import varispeed as vs
-    values = []
-    for item in str(spec).split(','):
-        item = item.strip()
-        try:
-            parts = [float(v) for v in item.split(':')]
-        except ValueError:
-            raise ValueError(f'--speeds: {item!r} is not a speed or a range lo:hi:inc')
-        if not all(np.isfinite(parts)):
-            raise ValueError(f'--speeds: {item!r} is outside the supported range: every number must be finite')
-        if len(parts) == 1:
-            values.append(parts[0])
-        elif len(parts) == 3:
-            lo, hi, inc = parts
-            if not (inc > 0 and lo <= hi):
-                raise ValueError(f'--speeds: the range {item!r} needs lo <= hi and inc > 0')
-            n = (hi - lo) / inc + 1e-9                             # (a float: a tiny inc makes it huge or infinite)
-            n = MAX_SPEEDS + 1 if n > MAX_SPEEDS else int(n) + 1
-            if n > MAX_SPEEDS:
-                raise ValueError(f'--speeds: the range {item!r} holds more than {MAX_SPEEDS} hypotheses; at most {MAX_SPEEDS} are taken')
-            values += [round(lo + k * inc, 10) for k in range(n)]
-        else:
-            raise ValueError(f'--speeds: {item!r} is not a speed or a range lo:hi:inc')
     out = []
-    for v in values:
+    for v in _grid(spec, '--speeds', 'speed', MAX_SPEEDS):
         if not vs.SPEED_MIN <= v <= vs.SPEED_MAX:                  # (a NaN fails the comparison too)
             raise ValueError(f'--speeds: speed {v!r} is outside the supported range {vs.SPEED_MIN} .. {vs.SPEED_MAX}')
         step = vs.step_for(v)
@@ -67,17 +81,39 @@ def parse_speeds(spec):
     return out
 
 
+def parse_tempos(spec):
+    """`--tempos`: the grammar of `--speeds` -> the hypotheses as the kernel takes them: rho = round(2^16 * tempo), the library rows
+    advanced per segment of the recording in 16.16 fixed point, a rho named twice kept once, sorted by |rho - 2^16| and then by
+    value, so that the kernel's tie rule (the hypothesis first in the list) means "nearest 1".  ValueError by name for anything
+    that is not such a list, for a tempo outside 0.8 .. 1.25 and for more than MAX_TEMPOS hypotheses."""
+    out = set()
+    for v in _grid(spec, '--tempos', 'tempo', MAX_TEMPOS):
+        if not TEMPO_MIN <= v <= TEMPO_MAX:
+            raise ValueError(f'--tempos: tempo {v!r} is outside the supported range {TEMPO_MIN} .. {TEMPO_MAX}')
+        out.add(int(round(TEMPO_ONE * v)))
+    if len(out) > MAX_TEMPOS:
+        raise ValueError(f'--tempos: {len(out)} hypotheses; at most {MAX_TEMPOS} are taken')
+    return sorted(out, key=lambda rho: (abs(rho - TEMPO_ONE), rho))
+
+
+def tempo_off(n, rho):
+    """off(n) of nafp_search_identify_tempo: the library rows that n segments of the recording advance under rho."""
+    return (int(n) * int(rho) + 32768) >> 16
+
+
 def select_across_speeds(matches):
     """The matches of every speed hypothesis (dicts with `recording`, `recording_span_s`, `score`, `speed`) -> the ones kept, per
-    recording (told apart by `_rec`, its place among the recordings, where a match carries one: a path may be given twice).  Candidates are taken by score descending, then |log speed| ascending, then speed ascending, then start of the
-    span; one is accepted unless its span overlaps an already accepted span of the same recording by more than half of the
+    recording (told apart by `_rec`, its place among the recordings, where a match carries one: a path may be given twice).  Candidates are taken by score descending, then |log speed| ascending, then |log tempo| ascending (`--tempos`; 1 where a
+    match carries none), then speed, tempo and start of the span ascending; one is accepted unless its span overlaps an already accepted span of the same recording by more than half of the
     shorter of the two.  Returned in the order of the recordings' first appearance, then by start of the span.  Pure host code."""
     import math
     which = lambda m: m.get('_rec', m['recording'])
     order = {}
     for m in matches:
         order.setdefault(which(m), len(order))
-    ranked = sorted(matches, key=lambda m: (-m['score'], abs(math.log(m['speed'])), m['speed'], m['recording_span_s'][0]))
+    tempo = lambda m: m.get('tempo', 1.0)                          # (`--tempos`: then the tempo nearer to 1, after the speed)
+    ranked = sorted(matches, key=lambda m: (-m['score'], abs(math.log(m['speed'])), abs(math.log(tempo(m))), m['speed'], tempo(m),
+                                            m['recording_span_s'][0]))
     kept = []
     for m in ranked:
         a0, a1 = m['recording_span_s']
@@ -112,33 +148,43 @@ def plan_windows(n_segments, window, window_hop):
     return np.asarray(rec, np.int64), np.asarray(s0, np.int64), np.asarray(ln, np.int64)
 
 
-def merge_windows(rec, s0, length, track, align, score, votes, min_score=None, align_tol=1):
+def merge_windows(rec, s0, length, track, align, score, votes, min_score=None, align_tol=1, rho=None):
     """Per-window best results -> matches.  Window w of recording rec[w] starts at segment s0[w]; its best result is
     (track[w], align[w], score[w], votes[w]), track -1 = none.  The alignment in the recording's frame is a_rec = align - s0: the
     library row the recording's segment 0 falls on.  Consecutive windows of one recording with the same track whose a_rec differ
     by at most `align_tol` from the window before merge into one match; a window without a result, or with a score below
     `min_score` (None: no threshold), is no match and breaks the run.  Returns a list of dicts: rec, seg0, seg1 (the segments
     [seg0, seg1) of the recording the match spans), track, a_rec (of the best-scoring window), score (mean), votes (minimum),
-    windows."""
+    windows.
+    rho (`--tempos`): the tempo hypothesis of each window's result, 16.16 fixed point.  Window w then continues the run of the
+    window before it if align_w is within `align_tol` of align_prev + off_prev(s0_w - s0_prev), the row the line of the window
+    before reaches at s0_w (`tempo_off`; with rho = 2^16 this is the rule above).  The hypothesis may differ from window to
+    window -- neighbouring ones cannot be told apart on a short window -- a match reports `rho`, that of its best-scoring
+    window, and a_rec is extrapolated along that window's line to the recording's segment 0."""
+    one = rho is None
     out, run, prev = [], None, None
     for w in range(len(rec)):
         ok = int(track[w]) >= 0 and np.isfinite(score[w]) and (min_score is None or float(score[w]) >= float(min_score))
-        a_rec = int(align[w]) - int(s0[w])
-        cur = (int(rec[w]), int(track[w]), a_rec) if ok else None
-        if cur is not None and prev is not None and cur[:2] == prev[:2] and abs(cur[2] - prev[2]) <= int(align_tol):
+        rho_w = TEMPO_ONE if one else int(rho[w])
+        cur = (int(rec[w]), int(track[w]), int(align[w]), int(s0[w]), rho_w) if ok else None
+        if (cur is not None and prev is not None and cur[:2] == prev[:2]
+                and abs(cur[2] - (prev[2] + tempo_off(cur[3] - prev[3], prev[4]))) <= int(align_tol)):
             run['seg1'] = int(s0[w]) + int(length[w])
-            run['_scores'].append(float(score[w])); run['_a'].append(a_rec)
+            run['_scores'].append(float(score[w])); run['_w'].append(cur)
             run['votes'] = min(run['votes'], int(votes[w]))
         else:
             run = None
             if cur is not None:
                 run = {'rec': cur[0], 'seg0': int(s0[w]), 'seg1': int(s0[w]) + int(length[w]), 'track': cur[1], 'votes': int(votes[w]),
-                       '_scores': [float(score[w])], '_a': [a_rec]}
+                       '_scores': [float(score[w])], '_w': [cur]}
                 out.append(run)
         prev = cur
     for m in out:
-        sc, al = m.pop('_scores'), m.pop('_a')
-        m['a_rec'] = al[int(np.argmax(sc))]
+        sc, ws = m.pop('_scores'), m.pop('_w')
+        _, _, al, at, rho_w = ws[int(np.argmax(sc))]
+        m['a_rec'] = al - tempo_off(at, rho_w)
+        if not one:
+            m['rho'] = rho_w
         m['score'] = float(np.mean(sc))
         m['windows'] = len(sc)
     return out
@@ -206,9 +252,11 @@ def fingerprint_recordings(cfg, checkpoint_name, checkpoint_index, files, step=N
     return rows, np.asarray(src.file_first, np.int64)
 
 
-def match_windows(flat, index, rows, rec_first, track_first, window, window_hop, k_probe, min_overlap, min_votes, n_short):
+def match_windows(flat, index, rows, rec_first, track_first, window, window_hop, k_probe, min_overlap, min_votes, n_short, rhos=None):
     """Top-k search of every recording row on `index`, then one nafp_search_identify launch over all windows on `flat` (the
-    resident fp32 rows).  Returns the window plan and the best result per window as numpy arrays."""
+    resident fp32 rows).  Returns the window plan and the best result per window as numpy arrays.  rhos (`--tempos`): the launch
+    is nafp_search_identify_tempo's over these hypotheses.  The last member returned is the tempo of each window's result (a member of
+    rhos, 2^16 where there is no result), None without rhos."""
     import torch
     rec, s0, ln = plan_windows(np.diff(rec_first), window, window_hop)
     dev = flat.device
@@ -217,17 +265,25 @@ def match_windows(flat, index, rows, rec_first, track_first, window, window_hop,
     ids = ids.to(torch.int32).contiguous()
     q0 = torch.from_numpy((rec_first[rec] + s0).astype(np.int32)).to(dev)
     tl = torch.from_numpy(ln.astype(np.int32)).to(dev)
-    track, align, score, votes, overlap, n_cand = flat.identify(q, ids, q0, tl, track_first, n_out=1, n_short=int(n_short),
-                                                                min_overlap=int(min_overlap), min_votes=int(min_votes),
-                                                                max_len=int(window))
+    kw = dict(n_out=1, n_short=int(n_short), min_overlap=int(min_overlap), min_votes=int(min_votes), max_len=int(window))
     host = lambda t: t.cpu().numpy()
-    return rec, s0, ln, host(track)[:, 0], host(align)[:, 0], host(score)[:, 0], host(votes)[:, 0], host(overlap)[:, 0], host(n_cand)
+    if rhos is None:
+        track, align, score, votes, overlap, n_cand = flat.identify(q, ids, q0, tl, track_first, **kw)
+        return rec, s0, ln, host(track)[:, 0], host(align)[:, 0], host(score)[:, 0], host(votes)[:, 0], host(overlap)[:, 0], host(n_cand), None
+    track, align, score, votes, overlap, n_cand, r = flat.identify_tempo(q, ids, q0, tl, track_first, rhos, **kw)
+    r = host(r)[:, 0]
+    rho = np.where(r >= 0, np.asarray(rhos, np.int64)[np.maximum(r, 0)], TEMPO_ONE)
+    return (rec, s0, ln, host(track)[:, 0], host(align)[:, 0], host(score)[:, 0], host(votes)[:, 0], host(overlap)[:, 0], host(n_cand),
+            rho)
 
 
 def identify(cfg, checkpoint_name, checkpoint_index, paths, index_type='l2', window=20, window_hop=10, k_probe=20,
-             min_overlap=4, min_votes=2, n_short=32, min_score=None, align_tol=1, output=None, emb_dir=None, speeds=None):
+             min_overlap=4, min_votes=2, n_short=32, min_score=None, align_tol=1, output=None, emb_dir=None, speeds=None,
+             tempos=None):
     """`run.py identify`.  Returns the dict written to identify.json.  speeds: the `--speeds` text, or None -- then the command
-    prints and writes exactly what it did before the option existed."""
+    prints and writes exactly what it did before the option existed.  tempos: the `--tempos` text, or None, likewise: without it
+    the matcher is nafp_search_identify as before, with it every window is matched under all tempo hypotheses in one launch of
+    nafp_search_identify_tempo, on the fingerprints of each speed hypothesis (the grid is the product of the two)."""
     from .eval_faiss import FlatL2Index, get_index, load_memmap_data
     hypotheses = None
     if speeds is not None:
@@ -235,6 +291,18 @@ def identify(cfg, checkpoint_name, checkpoint_index, paths, index_type='l2', win
             hypotheses = parse_speeds(speeds)                      # before any GPU call
         except ValueError as e:
             sys.exit(f'identify: {e}')
+    rhos = None
+    if tempos is not None:
+        try:
+            rhos = parse_tempos(tempos)                            # before any GPU call
+        except ValueError as e:
+            sys.exit(f'identify: {e}')
+        if int(window) * int(k_probe) * len(rhos) > MAX_SLOTS:
+            sys.exit(f'identify: --window {window} x --k_probe {k_probe} x {len(rhos)} tempos (--tempos) = '
+                     f'{int(window) * int(k_probe) * len(rhos)} slots per window; the matcher (nafp_search_identify_tempo) takes at '
+                     f'most {MAX_SLOTS}')
+        # every true alignment has near-duplicates at the neighbouring tempos, which would crowd it out of a shortlist of n_short
+        n_short = min(MAX_SHORT, int(n_short) * len(rhos))
     if int(window) * int(k_probe) > MAX_SLOTS:
         sys.exit(f'identify: --window {window} x --k_probe {k_probe} = {int(window) * int(k_probe)} slots per window; the matcher '
                  f'(nafp_search_identify) takes at most {MAX_SLOTS}')
@@ -273,8 +341,8 @@ def identify(cfg, checkpoint_name, checkpoint_index, paths, index_type='l2', win
     for step, speed in hypotheses or [(vs.ONE, 1.0)]:
         # the hypothesis "as it is" runs the path without a step: no varispeed launch
         rows, rec_first = fingerprint_recordings(cfg, checkpoint_name, checkpoint_index, files, None if step == vs.ONE else step, model)
-        rec, s0, ln, track, align, score, votes, overlap, n_cand = match_windows(
-            flat, index, rows, rec_first, track_first, window, window_hop, k_probe, min_overlap, min_votes, n_short)
+        rec, s0, ln, track, align, score, votes, overlap, n_cand, rho = match_windows(
+            flat, index, rows, rec_first, track_first, window, window_hop, k_probe, min_overlap, min_votes, n_short, rhos)
         n_windows += int(len(rec))
         sigma = step / vs.ONE                                      # recording seconds per stretched second
         best = [None] * len(files)
@@ -282,7 +350,7 @@ def identify(cfg, checkpoint_name, checkpoint_index, paths, index_type='l2', win
             if int(track[w]) >= 0 and np.isfinite(score[w]) and (best[int(rec[w])] is None or float(score[w]) > best[int(rec[w])]):
                 best[int(rec[w])] = float(score[w])
         best_scores.append(best)
-        for m in merge_windows(rec, s0, ln, track, align, score, votes, min_score, align_tol):
+        for m in merge_windows(rec, s0, ln, track, align, score, votes, min_score, align_tol, rho):
             tr = m['track']
             span = [m['seg0'] * hop_s, (m['seg1'] - 1) * hop_s + dur_s]
             row = {'_rec': m['rec'], 'recording': files[m['rec']],
@@ -292,11 +360,16 @@ def identify(cfg, checkpoint_name, checkpoint_index, paths, index_type='l2', win
                    'score': m['score'], 'min_votes': m['votes'], 'windows': m['windows']}
             if hypotheses is not None:
                 row['speed'] = speed
+            if rhos is not None:
+                row['tempo'] = m['rho'] / TEMPO_ONE                # library seconds per second of the (speed-undone) recording
             result_matches.append(row)
     if hypotheses is not None:
         result_matches = select_across_speeds(result_matches)
 
     sp_head, sp_cell = (f' {"speed":>7s}', lambda row: f' {row["speed"]:7.4f}') if hypotheses is not None else ('', lambda row: '')
+    if rhos is not None:
+        sp_head, speed_cell = sp_head + f' {"tempo":>7s}', sp_cell
+        sp_cell = lambda row: speed_cell(row) + f' {row["tempo"]:7.4f}'
     print(f'{"recording":<32s} {"from":>8s} {"to":>8s}  {"track":<32s} {"at":>9s} {"score":>7s} {"votes":>5s} {"win":>4s}{sp_head}')
     for row in result_matches:
         print(f'{os.path.basename(row["recording"])[-32:]:<32s} {row["recording_span_s"][0]:8.1f} {row["recording_span_s"][1]:8.1f}  '
@@ -316,6 +389,9 @@ def identify(cfg, checkpoint_name, checkpoint_index, paths, index_type='l2', win
         # n_windows counts every hypothesis' windows; speed_best_scores[h][r]: the best window score of recording r under hypothesis h
         result['speeds'] = [speed for _, speed in hypotheses]
         result['speed_best_scores'] = best_scores
+    if rhos is not None:
+        # n_short above is the shortlist the launch used; the time scale of a match is speed x tempo
+        result['tempos'] = [rho / TEMPO_ONE for rho in rhos]
     out_path = output or f'{emb_dir}identify.json'
     with open(out_path, 'w') as f:
         json.dump(result, f, indent=1)

@@ -5,6 +5,7 @@
     python run.py evaluate NAME INDEX [-c CONFIG] [-i ivfpq] [-t icassp] [--test_seq_len '1 3 5 9 11 19']
     python run.py identify NAME INDEX PATH... [-c CONFIG] [-i L2] [--window 20] [--window_hop 10] [--k_probe 20] [--min_overlap 4]
                            [--min_votes 2] [--n_short 32] [--min_score X] [--align_tol 1] [--output FILE] [--speeds 0.96,1,1.04]
+                           [--tempos 0.96,1,1.04]
 
 The command / argument / option surface equals the reference's run.py:13-162 (held to it by
 tests/test_golden_cli.py; one declared extension: `train --synthetic`; `evaluate -i` keeps the reference's default
@@ -164,6 +165,9 @@ _IDENTIFY = [
     (('--speeds',), dict(default=None, type=click.STRING,
                          help='speed hypotheses for recordings played fast or slow (tempo and pitch together): a comma list and / or '
                               'ranges lo:hi:inc, e.g. 0.96,1,1.04 or 0.94:1.06:0.01; at most 64, each within 0.8 .. 1.25; default: none')),
+    (('--tempos',), dict(default=None, type=click.STRING,
+                         help='tempo hypotheses for time-stretched recordings (tempo changed, pitch kept), all matched in one launch: the '
+                              'grammar of --speeds; at most 16, each within 0.8 .. 1.25; with --speeds 1/p a pitch shift by p; default: none')),
 ]
 
 
@@ -178,14 +182,14 @@ def extensions():
 @click.argument('paths', nargs=-1, required=True)
 @_with(_IDENTIFY)
 def identify(checkpoint_name, checkpoint_index, paths, config, index_type, window, window_hop, k_probe, min_overlap, min_votes,
-             n_short, min_score, align_tol, output, speeds):
+             n_short, min_score, align_tol, output, speeds, tempos):
     """Name the track and the offset of unlabelled recordings (files or directories) against the fingerprints `generate` wrote
     with NAFP_TRACK_TABLE=1."""
     from neural_audio_fp_amd.eval.identify import identify as run_identify
     cfg = load_config(config)
     run_identify(cfg, checkpoint_name, checkpoint_index, list(paths), index_type=index_type, window=window, window_hop=window_hop,
                  k_probe=k_probe, min_overlap=min_overlap, min_votes=min_votes, n_short=n_short, min_score=min_score,
-                 align_tol=align_tol, output=output, speeds=speeds)
+                 align_tol=align_tol, output=output, speeds=speeds, tempos=tempos)
 
 
 main = click.CommandCollection(sources=[cli, extensions], help=cli.help)

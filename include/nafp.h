@@ -875,6 +875,26 @@ int nafp_search_topk_l2(const float* query, int64_t n_query, const float* index,
                         int64_t n_index, int dim, int k, float* out_dist, int32_t* out_ids,
                         void* workspace, int64_t workspace_bytes, void* stream);
 
+/* nafp_search_topk_l2 with a row range left out per query: excl (n_query, 2) int32, a DEVICE array of pairs (lo, hi); query q
+ * gets the result nafp_search_topk_l2 would give on the index rows outside [lo_q, hi_q), with the ids of the whole index.  A
+ * self-join of a library (every row a query, its own track excluded) is the use: the exclusion happens inside the selection,
+ * before a row enters a list of k, so the k survivors are kept however many excluded rows are nearer.
+ *   - unchanged from nafp_search_topk_l2: the float32 key q.x - |x|^2/2 and the order (key descending, then id ascending), the
+ *     distance written, the padding (id -1, distance +inf) when fewer than k rows survive, the NaN / Inf rules, k <= 32;
+ *   - lo and hi are clipped to [0, n_index] when they are loaded, each by comparisons (no difference is formed, so nothing
+ *     overflows): ANY int32 pair is legal, lo > hi, negative values, INT32_MIN / INT32_MAX included.  A pair with lo >= hi
+ *     after clipping excludes nothing; (INT32_MIN, INT32_MAX) excludes every row.  excl is only ever compared with row
+ *     numbers: it is never an address or an index into `index`;
+ *   - with every range empty out_dist and out_ids equal nafp_search_topk_l2's byte for byte;
+ *   - bit-identical from run to run; a query's row does not depend on what shares the launch;
+ *   - workspace: nafp_search_workspace_bytes(n_query, n_index, k), the same split plan and the same merge.
+ * Status, before any GPU call, as nafp_search_topk_l2: NAFP_ERR_INVALID_ARG for a null pointer (excl included), n_query < 0,
+ * n_index <= 0 or k <= 0; NAFP_ERR_UNSUPPORTED for dim outside 64 / 128 / 256, k > 32, n_index >= 2^31 or n_query > 2^30;
+ * n_query == 0 returns NAFP_OK without a launch; NAFP_ERR_WORKSPACE for a workspace that is too small. */
+int nafp_search_topk_l2_excl(const float* query, int64_t n_query, const float* index, const float* aux,
+                             int64_t n_index, int dim, int k, const int32_t* excl, float* out_dist, int32_t* out_ids,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+
 /* out_scores[t, s] = mean_{i < min(task_len[t], n_index - c)} query[task_q0[t] + i] . index[c + i]
  * for the candidate sequence start c = cand[t, s] (>= 0; -1 -> -inf): np.mean(np.diag(np.dot(q,
  * index[c:c+l].T))) of eval_faiss.py:224-230.  All device pointers. */

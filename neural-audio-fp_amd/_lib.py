@@ -128,6 +128,8 @@ PROTOTYPES = {
     'nafp_search_workspace_bytes': (c_i64, [c_i64, c_i64, c_int]),
     'nafp_search_topk_l2': (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int, c_int, c_void_p, c_void_p,
                                     c_void_p, c_i64, c_void_p]),
+    'nafp_search_topk_l2_excl': (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_i64, c_void_p]),
     'nafp_search_seq_scores': (c_int, [c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_int,
                                        c_void_p, c_void_p]),
     'nafp_search_seq_match': (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_i64, c_int,

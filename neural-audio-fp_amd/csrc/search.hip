@@ -15,6 +15,8 @@
 //                              query and 16 index rows per block: it keeps that query's running top-K
 //                              as a sorted register list (threshold test per score, unrolled insertion
 //                              only when a score beats the K-th best).  blockIdx.y splits the index.
+//   search_topk_excl_kernel<D,K>  the same body with one excluded row range per query (nafp_search_topk_l2_excl): the lane's
+//                              clipped (lo, hi) in two registers, tested only where a score has beaten the K-th best
 //   search_merge_kernel<K>     merges the 2 x splits partial lists of a query (key desc, id asc)
 //   ivf_flat_scan_kernel<D,K>  the same body over one inverted list's rows for the queries that probe it (ivf.hip)
 //   search_seq_score_kernel<D> mean_i q[t+i] . x[c+i] for candidate sequence starts c (eval_faiss.py:221-230)
@@ -59,13 +61,15 @@ __global__ __launch_bounds__(256) void search_half_norms_kernel(const float* __r
 
 constexpr int TILE_ROWS = 64;
 
-template <int D, int K>
+template <int D, int K, bool EXCL = false>
 __device__ __forceinline__ void search_topk_body(
         const float* __restrict__ Q, const float* __restrict__ X, const float* __restrict__ hn,
         float* __restrict__ out_key, int* __restrict__ out_id, int nq, int64_t N, int tiles_per_split, int n_lists,
-        int qb, int split, const int* __restrict__ qmap) {
+        int qb, int split, const int* __restrict__ qmap, const int* __restrict__ excl = nullptr) {
     // qb / split: the query block and index split of this workgroup (blockIdx.x / .y for the exact search); qmap: the row of
     // Q that query qn of the block reads (nullptr: row qn; the IVF scan reads its list's queries through it, ivf.hip)
+    // EXCL (nafp_search_topk_l2_excl): excl (nq, 2) = the row range [lo, hi) query qn never takes.  A lane owns one query, so the
+    // clipped pair is two registers per lane, and the range test sits where a score has already beaten the K-th best.
     constexpr int CH = D / 4;                        // 16-B chunks per row
     constexpr int SWZ = (CH < 32 ? CH : 32) - 1;      // chunk swizzle mask: the row's low bits -- the same for row rl and row 32 + rl, which share `aoff` (d = 256 has 64 chunks)
     constexpr int RPI = 64 / CH;                     // rows per DMA wave-instruction
@@ -86,6 +90,15 @@ __device__ __forceinline__ void search_topk_body(
 #pragma unroll
     for (int kk = 0; kk < D / 8; ++kk)
         qr[kk] = qn < nq ? *(const float4*)(Q + (int64_t)(qmap ? qmap[qn] : qn) * D + 8 * kk + 4 * hh) : make_float4(0.f, 0.f, 0.f, 0.f);
+
+    // the excluded rows of this lane's query, clipped to [0, N] as plain comparisons (any int32 pair is legal; lo >= hi: none)
+    int ex_lo = 0, ex_hi = 0;
+    if constexpr (EXCL) {
+        if (qn < nq) {
+            ex_lo = std::min(std::max(excl[2 * (int64_t)qn], 0), (int)N);
+            ex_hi = std::min(std::max(excl[2 * (int64_t)qn + 1], 0), (int)N);
+        }
+    }
 
     float sc[K]; int id[K];
 #pragma unroll
@@ -153,12 +166,14 @@ __device__ __forceinline__ void search_topk_body(
                     const float key = acc[mi][r];                                                   \
                     if (key > sc[K - 1]) {                                                          \
                         const int nid = base_id + mi * 32 + 8 * (r >> 2) + (r & 3) + 4 * hh;        \
-                        _Pragma("unroll") for (int j = K - 1; j >= 1; --j) {                        \
-                            const bool cj = key > sc[j], cp = key > sc[j - 1];                      \
-                            id[j] = cj ? (cp ? id[j - 1] : nid) : id[j];                            \
-                            sc[j] = cj ? (cp ? sc[j - 1] : key) : sc[j];                            \
+                        if (!EXCL || nid < ex_lo || nid >= ex_hi) {                                 \
+                            _Pragma("unroll") for (int j = K - 1; j >= 1; --j) {                    \
+                                const bool cj = key > sc[j], cp = key > sc[j - 1];                  \
+                                id[j] = cj ? (cp ? id[j - 1] : nid) : id[j];                        \
+                                sc[j] = cj ? (cp ? sc[j - 1] : key) : sc[j];                        \
+                            }                                                                       \
+                            if (key > sc[0]) { sc[0] = key; id[0] = nid; }                          \
                         }                                                                           \
-                        if (key > sc[0]) { sc[0] = key; id[0] = nid; }                              \
                     }                                                                               \
                 }                                                                                   \
             }                                                                                       \
@@ -192,6 +207,20 @@ __global__ __launch_bounds__(256, 1) void search_topk_kernel_d256(
         const float* __restrict__ Q, const float* __restrict__ X, const float* __restrict__ hn,
         float* __restrict__ out_key, int* __restrict__ out_id, int nq, int64_t N, int tiles_per_split, int n_lists) {
     search_topk_body<256, K>(Q, X, hn, out_key, out_id, nq, N, tiles_per_split, n_lists, blockIdx.x, blockIdx.y, nullptr);
+}
+// The masked search (nafp_search_topk_l2_excl): the same body with the per-query range test compiled in.  The partial lists have
+// the layout of the unmasked kernels, so search_merge_kernel serves both.
+template <int D, int K>
+__global__ __launch_bounds__(256, 2) void search_topk_excl_kernel(
+        const float* __restrict__ Q, const float* __restrict__ X, const float* __restrict__ hn, const int* __restrict__ excl,
+        float* __restrict__ out_key, int* __restrict__ out_id, int nq, int64_t N, int tiles_per_split, int n_lists) {
+    search_topk_body<D, K, true>(Q, X, hn, out_key, out_id, nq, N, tiles_per_split, n_lists, blockIdx.x, blockIdx.y, nullptr, excl);
+}
+template <int K>
+__global__ __launch_bounds__(256, 1) void search_topk_excl_kernel_d256(
+        const float* __restrict__ Q, const float* __restrict__ X, const float* __restrict__ hn, const int* __restrict__ excl,
+        float* __restrict__ out_key, int* __restrict__ out_id, int nq, int64_t N, int tiles_per_split, int n_lists) {
+    search_topk_body<256, K, true>(Q, X, hn, out_key, out_id, nq, N, tiles_per_split, n_lists, blockIdx.x, blockIdx.y, nullptr, excl);
 }
 
 // IVF-Flat scan (ivf.hip, nafp_ivf_flat_search): the body above over ONE inverted list's rows (padded to whole tiles, +inf half
@@ -835,6 +864,22 @@ static int launch_topk(const float* Q, int nq, const float* X, const float* hn, 
     return NAFP_OK;
 }
 
+template <int D, int K>
+static int launch_topk_excl(const float* Q, int nq, const float* X, const float* hn, const int* excl, int64_t N, float* pk, int* pi,
+                            int splits, int tps, hipStream_t st) {
+    const int lds = 2 * TILE_ROWS * D * (int)sizeof(float);
+    const dim3 grid((unsigned)((nq + 127) / 128), (unsigned)splits);
+    if constexpr (D == 256) {
+        NAFP_HIP_CHECK(hipFuncSetAttribute((const void*)search_topk_excl_kernel_d256<K>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        search_topk_excl_kernel_d256<K><<<grid, 256, lds, st>>>(Q, X, hn, excl, pk, pi, nq, N, tps, 2 * splits);
+    } else {
+        NAFP_HIP_CHECK(hipFuncSetAttribute((const void*)search_topk_excl_kernel<D, K>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        search_topk_excl_kernel<D, K><<<grid, 256, lds, st>>>(Q, X, hn, excl, pk, pi, nq, N, tps, 2 * splits);
+    }
+    NAFP_LAUNCH_CHECK();
+    return NAFP_OK;
+}
+
 static void plan_splits(int nq, int64_t N, int K, int* splits, int* tps) {
     const int64_t n_tiles = (N + TILE_ROWS - 1) / TILE_ROWS;
     const int q_tiles = (nq + 127) / 128;
@@ -892,6 +937,35 @@ extern "C" int nafp_search_topk_l2(const float* query, int64_t n_query, const fl
                                       : launch_topk<256, 32>(query, (int)n_query, index, aux, n_index, pk, pi, splits, tps, st);
     else            rc = K == 20 ? launch_topk<64, 20>(query, (int)n_query, index, aux, n_index, pk, pi, splits, tps, st)
                                  : launch_topk<64, 32>(query, (int)n_query, index, aux, n_index, pk, pi, splits, tps, st);
+    if (rc != NAFP_OK) return rc;
+    const int M = 2 * splits * K;
+    if (K == 20) search_merge_kernel<20><<<(unsigned)n_query, 64, M * 8, st>>>(pk, pi, query, out_dist, out_ids, 2 * splits, dim, k);
+    else         search_merge_kernel<32><<<(unsigned)n_query, 64, M * 8, st>>>(pk, pi, query, out_dist, out_ids, 2 * splits, dim, k);
+    NAFP_LAUNCH_CHECK();
+    return NAFP_OK;
+}
+
+extern "C" int nafp_search_topk_l2_excl(const float* query, int64_t n_query, const float* index, const float* aux,
+                                        int64_t n_index, int dim, int k, const int32_t* excl, float* out_dist, int32_t* out_ids,
+                                        void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!query || !index || !aux || !excl || !out_dist || !out_ids || !workspace || n_query < 0 || n_index <= 0 || k <= 0)
+        return NAFP_ERR_INVALID_ARG;
+    if ((dim != 64 && dim != 128 && dim != 256) || k > 32 || n_index >= ((int64_t)1 << 31) || n_query > (1 << 30)) return NAFP_ERR_UNSUPPORTED;
+    if (n_query == 0) return NAFP_OK;
+    if (workspace_bytes < nafp_search_workspace_bytes(n_query, n_index, k)) return NAFP_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int K = k <= 20 ? 20 : 32;
+    int splits, tps;
+    plan_splits((int)n_query, n_index, K, &splits, &tps);
+    char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    float* pk = (float*)ws;
+    int* pi = (int*)(ws + (int64_t)n_query * 2 * splits * K * 4);
+#define NAFP_TOPK_X(D_, K_) launch_topk_excl<D_, K_>(query, (int)n_query, index, aux, excl, n_index, pk, pi, splits, tps, st)
+    int rc;
+    if (dim == 128) rc = K == 20 ? NAFP_TOPK_X(128, 20) : NAFP_TOPK_X(128, 32);
+    else if (dim == 256) rc = K == 20 ? NAFP_TOPK_X(256, 20) : NAFP_TOPK_X(256, 32);
+    else rc = K == 20 ? NAFP_TOPK_X(64, 20) : NAFP_TOPK_X(64, 32);
+#undef NAFP_TOPK_X
     if (rc != NAFP_OK) return rc;
     const int M = 2 * splits * K;
     if (K == 20) search_merge_kernel<20><<<(unsigned)n_query, 64, M * 8, st>>>(pk, pi, query, out_dist, out_ids, 2 * splits, dim, k);

@@ -114,6 +114,30 @@ class FlatL2Index:
                                                      _lib.current_stream()), 'search_topk_l2')
         return D, I
 
+    def search_device_excl(self, q, k, excl):
+        """`search_device` with a row range left out per query (nafp_search_topk_l2_excl, include/nafp.h): excl (nq, 2) CUDA
+        int32, query r gets the k nearest rows outside [excl[r, 0], excl[r, 1]).  Any pair is legal; lo >= hi excludes nothing."""
+        q = _lib.require_cuda(q, 'q').float().contiguous()
+        excl = _lib.require_cuda(excl, 'excl')
+        if self.ntotal == 0:
+            raise ValueError('empty index')
+        nq = q.shape[0]
+        if excl.dtype != torch.int32 or excl.dim() != 2 or tuple(excl.shape) != (nq, 2):
+            raise TypeError('search_device_excl: excl (nq, 2) int32')
+        excl = excl.contiguous()
+        aux = self._prepare()
+        D = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        I = torch.empty((nq, k), dtype=torch.int32, device=self.device)
+        need = int(self._lib.nafp_search_workspace_bytes(nq, self.ntotal, k))
+        if need < 0:
+            raise NotImplementedError(f'k = {k} (the HIP search keeps k <= 32 results per query)')
+        ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.nafp_search_topk_l2_excl(_lib.ptr(q), nq, _lib.ptr(self._x), _lib.ptr(aux), self.ntotal, self.d,
+                                                          int(k), _lib.ptr(excl), _lib.ptr(D), _lib.ptr(I), _lib.ptr(ws), need,
+                                                          _lib.current_stream()), 'search_topk_l2_excl')
+        return D, I
+
     def search(self, q, k):
         """faiss signature: numpy in, (D float32, I int64) numpy out."""
         qd = torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32)).to(self.device)

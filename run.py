@@ -6,6 +6,8 @@
     python run.py identify NAME INDEX PATH... [-c CONFIG] [-i L2] [--window 20] [--window_hop 10] [--k_probe 20] [--min_overlap 4]
                            [--min_votes 2] [--n_short 32] [--min_score X] [--align_tol 1] [--output FILE] [--speeds 0.96,1,1.04]
                            [--tempos 0.96,1,1.04]
+    python run.py duplicates NAME INDEX [-c CONFIG] [--window 20] [--window_hop 10] [--k_probe 20] [--min_overlap 4] [--min_votes 2]
+                           [--n_short 32] [--min_score X] [--align_tol 1] [--min_coverage 0] [--chunk_rows 1048576] [--output FILE]
 
 The command / argument / option surface equals the reference's run.py:13-162 (held to it by
 tests/test_golden_cli.py; one declared extension: `train --synthetic`; `evaluate -i` keeps the reference's default
@@ -190,6 +192,40 @@ def identify(checkpoint_name, checkpoint_index, paths, config, index_type, windo
     run_identify(cfg, checkpoint_name, checkpoint_index, list(paths), index_type=index_type, window=window, window_hop=window_hop,
                  k_probe=k_probe, min_overlap=min_overlap, min_votes=min_votes, n_short=n_short, min_score=min_score,
                  align_tol=align_tol, output=output, speeds=speeds, tempos=tempos)
+
+
+_DUPLICATES = [
+    (('--config', '-c'), dict(default='default', required=False, type=click.STRING)),
+    (('--window',), dict(default=20, type=click.INT, help='analysis window in segments (window x k_probe <= 8192)')),
+    (('--window_hop',), dict(default=10, type=click.INT, help='segments between the starts of consecutive windows')),
+    (('--k_probe',), dict(default=20, type=click.INT, help='search results per segment, 1..32, none of them from the own track')),
+    (('--min_overlap',), dict(default=4, type=click.INT, help='segments a window must share with a track')),
+    (('--min_votes',), dict(default=2, type=click.INT, help='search results that must agree on (track, alignment)')),
+    (('--n_short',), dict(default=32, type=click.INT, help='candidates scored per window, 1..256')),
+    (('--min_score',), dict(default=None, type=click.FLOAT, help='a window whose best score is below this is no match; default: no threshold')),
+    (('--align_tol',), dict(default=1, type=click.INT, help='segments by which the alignment of consecutive windows, and the offsets '
+                                                            'of the two directions of a pair, may differ')),
+    (('--min_coverage',), dict(default=0.0, type=click.FLOAT, help='share of the shorter track a pair must span to link its tracks '
+                                                                   'into a group; default 0: every pair links')),
+    (('--chunk_rows',), dict(default=1 << 20, type=click.INT, help='rows searched per launch, in whole tracks; the output does not depend on it')),
+    (('--output',), dict(default=None, type=click.STRING, help='where duplicates.json goes; default next to the .mm files')),
+]
+
+
+@extensions.command()
+@click.argument('checkpoint_name', required=True)
+@click.argument('checkpoint_index', required=True)
+@_with(_DUPLICATES)
+def duplicates(checkpoint_name, checkpoint_index, config, window, window_hop, k_probe, min_overlap, min_votes, n_short, min_score,
+               align_tol, min_coverage, chunk_rows, output):
+    """Find the tracks the library holds more than once, from the fingerprints and track tables `generate` wrote with
+    NAFP_TRACK_TABLE=1: no model, no audio.  Always on the exact index (there is no -i): only the exact search can leave a row's
+    own track out of its results."""
+    from neural_audio_fp_amd.eval.duplicates import duplicates as run_duplicates
+    cfg = load_config(config)
+    run_duplicates(cfg, checkpoint_name, checkpoint_index, window=window, window_hop=window_hop, k_probe=k_probe,
+                   min_overlap=min_overlap, min_votes=min_votes, n_short=n_short, min_score=min_score, align_tol=align_tol,
+                   min_coverage=min_coverage, chunk_rows=chunk_rows, output=output)
 
 
 main = click.CommandCollection(sources=[cli, extensions], help=cli.help)

@@ -573,6 +573,16 @@ int nafp_encoder_forward_raw(nafp_encoder* enc, const float* raw_feat, const flo
                              int segment_norm, int64_t n_seg, void* workspace, int64_t workspace_bytes,
                              float* out_flat, float* out_emb, int l2norm, void* stream);
 
+/* DIAGNOSTIC, for tests that compare two forms of the first conv bit for bit (the forward reuses z0's buffer two layers later); not
+ * part of the inference interface.  The first conv (b0.conv1x3) of nafp_encoder_forward / _forward_raw alone, in the form the handle's
+ * options select (group_stat may be NULL: finished features): z0 (n_seg, in_f, t_out, c0) = gamma0 . ELU(conv + bias),
+ * nafp_encoder_conv0_numel floats per segment, and the layer's LayerNorm statistics as the next conv reads them, two 64-bit
+ * fixed-point sums per segment (stats_out: 2 * n_seg, zeroed by the call on `stream`).  As in the forward, a handle created with
+ * another normalisation than layer_norm2d drops finite partial sums beyond the fixed-point range instead of poisoning the sample. */
+int64_t nafp_encoder_conv0_numel(const nafp_encoder* enc);
+int nafp_encoder_conv0(nafp_encoder* enc, const float* feat, const float* group_stat, int group_size, int segment_norm,
+                       int64_t n_seg, float* z0_out, long long* stats_out, void* stream);
+
 /* Per-kernel timing of nafp_encoder_forward with HIP events recorded on the
  * caller's stream (bench.py's roofline leg).  enable(max_forwards > 0) allocates a
  * ring of event sets, one per forward call; enable(0) turns it off.  read() waits
@@ -694,6 +704,21 @@ int nafp_encoder_grad_group_wait(nafp_encoder* enc, int group, void* stream);
  * bit-identical (tests/test_gpu_generate.py, tools/x6_determinism_check*.py).  A foreign kernel holding such instructions must not
  * run on the device while a forward with this option is in flight.  The fp32 path (f32 matrix instructions) does not disturb anything. */
 #define NAFP_OPT_BF16X3 3
+/* NAFP_OPT_NONMATRIX: a mask of NAFP_NONMATRIX_* bits, one per leaner form of a part of the forward pass OUTSIDE the GEMM K-loops.  Every
+ * bit leaves every byte of every result and of the per-layer statistics as it is (tests/test_gpu_nonmatrix_equal.py compares both
+ * forms in one process); the default is NAFP_NONMATRIX_DEFAULT, 0 selects the earlier forms.
+ *   CONV0        b0.conv1x3 as straight-line code: counted waits instead of a full drain per batch of positions, inputs staged with
+ *                their zero padding, no per-position division (conv0_lean_kernel, conv.hip).
+ *                Taken at the default 16 rows per workgroup only: with the A/B knob NAFP_CONV0_ROWS at another value, and in the
+ *                training forward, conv0_kernel runs whatever this bit says (same bytes).
+ *   KEEP_OWN     the two-part split-K launches that finish in-kernel: the last arriver adds the other part to the accumulators it
+ *                still holds instead of storing its own part and reading both back (conv_gemm_body, EPI 4).
+ * The process-wide default can be set with the environment variable NAFP_NONMATRIX (a mask, read when a handle is created). */
+#define NAFP_OPT_NONMATRIX 8
+#define NAFP_NONMATRIX_CONV0 1
+#define NAFP_NONMATRIX_KEEP_OWN 2
+#define NAFP_NONMATRIX_ALL 3
+#define NAFP_NONMATRIX_DEFAULT NAFP_NONMATRIX_ALL
 /* Options are host-side state of the handle: set them while no pass of the handle is being enqueued from another thread; passes already
  * enqueued keep what they were launched with.  (NAFP_OPT_BF16X3 = 2 allocates its split weights, 1.5 x the packed conv kernels, on first use.) */
 int nafp_encoder_set_option(nafp_encoder* enc, int option, int value);

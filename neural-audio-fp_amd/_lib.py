@@ -89,6 +89,8 @@ PROTOTYPES = {
     'nafp_encoder_forward': (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_int, c_void_p]),
     'nafp_encoder_forward_raw': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_i64, c_void_p, c_i64, c_void_p, c_void_p,
                                          c_int, c_void_p]),
+    'nafp_encoder_conv0_numel': (c_i64, [c_void_p]),
+    'nafp_encoder_conv0': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_i64, c_void_p, c_void_p, c_void_p]),
     'nafp_encoder_profile_enable': (c_int, [c_void_p, c_int]),
     'nafp_encoder_profile_count': (c_int, [c_void_p]),
     'nafp_encoder_profile_coarse': (c_int, [c_void_p, c_int]),

@@ -147,6 +147,8 @@ struct nafp_encoder {
     // optional per-kernel event timing (nafp_encoder_profile_*)
     std::vector<hipEvent_t> prof_events;  // (max_forwards, NAFP_PROF_EV): [conv0 a, b | conv j start, stop (j = 1..15) | tail a, b]
     int prof_max = 0, prof_count = 0;
+    // NAFP_OPT_NONMATRIX (default: NAFP_NONMATRIX env, else NAFP_NONMATRIX_DEFAULT): which leaner forms of the forward's non-GEMM parts run (same bytes either way)
+    int opt_nonmatrix = []() { const char* v = getenv("NAFP_NONMATRIX"); return v ? (int)strtol(v, nullptr, 0) & NAFP_NONMATRIX_ALL : NAFP_NONMATRIX_DEFAULT; }();
     int opt_bf16x3 = 0;                   // NAFP_OPT_BF16X3 (experimental): 0 off, 1 hi / lo split with 3 products, 2 exact 3-way split with 6 products
     // value 2: the packed conv kernels split into three bf16 terms (conv.hip, split_weights_multi_kernel), refreshed by the first forward after a
     // set_weights; one allocation of its own, made when the option is first switched on
@@ -421,6 +423,9 @@ extern "C" int nafp_encoder_set_option(nafp_encoder* e, int option, int value) {
             if (value < 0 || value > 2) return NAFP_ERR_INVALID_ARG;
             e->opt_fused_ln_bwd = value; return NAFP_OK;
         case NAFP_OPT_BWD_OVERLAP: e->opt_bwd_overlap = value < 0 ? 0 : (value > 2 ? 1 : value); return NAFP_OK;
+        case NAFP_OPT_NONMATRIX:
+            if (value < 0 || (value & ~NAFP_NONMATRIX_ALL)) return NAFP_ERR_INVALID_ARG;
+            e->opt_nonmatrix = value; return NAFP_OK;
         case NAFP_OPT_SMALLNET: return NAFP_OK;          // retired in round 6 (the persistent small-layer launch lost to the per-layer launches at every setting): accepted, ignored
         case NAFP_OPT_DEBUG_SIDE_DELAY:       // test hooks, not in include/nafp.h: refused outside a test process (round-5 ADVICE)
         case NAFP_OPT_DEBUG_SW_DELAY: {
@@ -660,6 +665,23 @@ extern "C" int nafp_encoder_forward_raw(nafp_encoder* e, const float* raw_feat, 
                                 out_flat, out_emb, l2norm, stream);
 }
 
+extern "C" int64_t nafp_encoder_conv0_numel(const nafp_encoder* e) {
+    return e ? (int64_t)e->geom[0].Fout * e->geom[0].Tout * e->geom[0].Cout : -1;
+}
+
+extern "C" int nafp_encoder_conv0(nafp_encoder* e, const float* feat, const float* gstat, int group_size, int segment_norm,
+                                  int64_t n_seg, float* z0_out, long long* stats_out, void* stream) {
+    if (!e || !feat || !z0_out || !stats_out || n_seg < 0) return NAFP_ERR_INVALID_ARG;
+    if (!e->has_weights) return NAFP_ERR_NO_WEIGHTS;
+    if (n_seg == 0) return NAFP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    { int wrc = wait_weights(e, st); if (wrc != NAFP_OK) return wrc; }
+    if (gstat && (group_size <= 0 || group_size > n_seg)) group_size = (int)std::min<int64_t>(n_seg, INT32_MAX);   // as nafp_encoder_forward_raw
+    NAFP_HIP_CHECK(hipMemsetAsync(stats_out, 0, sizeof(stat_t) * 2 * n_seg, st));
+    return launch_conv0(feat, e->d_w[0], e->d_bias[0], e->d_gamma[0], z0_out, nullptr, (stat_t*)stats_out, n_seg, e->geom[0], st,
+                        gstat, group_size, segment_norm & 1, e->norm != NAFP_NORM_LAYER2D, (e->opt_nonmatrix & NAFP_NONMATRIX_CONV0) != 0);
+}
+
 static int encoder_forward_impl(nafp_encoder* e, const float* feat, const float* gstat, int group_size, int segment_norm,
                                 int64_t n_seg, void* workspace, int64_t workspace_bytes, float* out_flat,
                                 float* out_emb, int l2norm, void* stream) {
@@ -709,7 +731,7 @@ static int encoder_forward_impl(nafp_encoder* e, const float* feat, const float*
                        e->geom[0].Tin <= 64 && (e->opt_bf16x3 != 2 || e->geom[1].Cin == 128);
     int rc = fuse0 ? launch_conv0_stats(feat, e->d_w[0], e->d_bias[0], stats, n_seg, e->geom[0], st, gstat, group_size, segment_norm)
                    : launch_conv0(feat, e->d_w[0], e->d_bias[0], e->d_gamma[0], bufA, nullptr, stats, n_seg, e->geom[0], st,
-                                  gstat, group_size, segment_norm, alt);
+                                  gstat, group_size, segment_norm, alt, (e->opt_nonmatrix & NAFP_NONMATRIX_CONV0) != 0);
     if (rc != NAFP_OK) return rc;
     if (!fuse0) { rc = row_pass(bufA, 0); if (rc != NAFP_OK) return rc; }
     if (ev && e->prof_coarse < 2) NAFP_HIP_CHECK(hipEventRecord(ev[1], st));
@@ -725,6 +747,7 @@ static int encoder_forward_impl(nafp_encoder* e, const float* feat, const float*
         if (!((x6_layers >> j) & 1)) a.bf16x3 = 0;
         if (a.bf16x3 == 2) { a.wp_hm = e->d_whm[j]; a.wp_l = e->d_wl[j]; }
         a.plan_b = fwd_plan_b();              // tile shape and split-K factor as at the reference launch size: results do not depend on n_seg
+        a.nonmatrix = e->opt_nonmatrix;
         if (j == 1 && fuse0) {
             a.x = nullptr; a.f0_feat = feat; a.f0_w = e->d_w[0]; a.f0_bias = e->d_bias[0];
             a.f0_gamma = e->d_gamma[0]; a.f0_geom = &e->geom[0];

@@ -177,14 +177,155 @@ __global__ __launch_bounds__(256) void conv0_kernel(
     }
 }
 
+// The same kernel as straight-line code (NAFP_NONMATRIX_CONV0; same values, same order of every float operation).  In
+// conv0_kernel<true, 16> every batch of NP positions starts with `s_waitcnt vmcnt(0)`: the gamma loads and the stores sit in
+// exec-masked branches (p < npos, v_out), so hipcc cannot count them and waits for everything -- the gamma loads of the NEXT
+// batch it has just issued and all stores of the previous one.  Each position also pays a 32-bit division (p / Tout) and
+// three exec-masked LDS reads for the padding tests.  Here
+//   - the gamma loads go through a buffer descriptor sized to the workgroup's positions (the prefetch beyond the last batch
+//     is out of range and loads 0), the full batches run without a branch and only a ragged last batch tests p < npos: the
+//     waits are counted, the stores of a batch stay in flight under the next one.  The stores go through plain pointers
+//     (every stored position exists).  OBSERVED, not explained: with `buffer_store_dwordx4 ... s<n> offen nt` (the batch
+//     offset in a scalar register; hipcc of ROCm 7.2, clang 22.0.0git roc-7.2.0) the first word of the 16 bytes came out
+//     replaced by other register contents in lanes 12-15 and 28-31 of each half wave -- only in workgroups that started
+//     on a compute unit already running others, never in the first one per unit, statistics always right.  It looks like
+//     a write of the store's data registers overtaking the store's read of them, but no ISA-level reproduction exists
+//     (record: profiles/nonmatrix_ab.md; tests/test_gpu_nonmatrix_equal.py runs 40 and 640 segments for that reason);
+//   - the input rows are staged WITH their zero padding (row stride RS0, `pad` zeros in front), so the three taps of a
+//     position are three unconditional LDS reads;
+//   - (row, frame) of a thread's next position follow from the previous one by an add and a wrap.
+// Inference only: a launch that keeps the pre-activation (v_out, the training forward) takes conv0_kernel.
+constexpr int RS0 = 72;                             // floats per staged row: pad + Tin <= RS0 and (Tout - 1) * stride + 3 <= RS0
+template <int ROWS0>
+__global__ __launch_bounds__(256) void conv0_lean_kernel(
+        const float* __restrict__ feat, const float* __restrict__ w3, const float* __restrict__ bias,
+        const float* __restrict__ gamma, float* __restrict__ y,
+        stat_t* __restrict__ stats, int F, int Tin, int Tout, int Cout, int stride, int pad,
+        const float* __restrict__ gstat, int group_size, int segment_norm, int ident_stats) {
+    constexpr int NP = 4;
+    typedef float f4nt __attribute__((ext_vector_type(4)));
+    __shared__ float s_x[ROWS0 * RS0];
+    __shared__ double red[8];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int blocks_per_sample = (F + ROWS0 - 1) / ROWS0;
+    const int64_t b = blockIdx.x / blocks_per_sample;
+    const int f0 = (blockIdx.x % blocks_per_sample) * ROWS0;
+    const int cgroups = Cout / 4;
+    const int pos_per_iter = 256 / cgroups;
+    const int cg = tid % cgroups, pslot = tid / cgroups;
+    const int rows = min(ROWS0, F - f0);
+    const int npos = rows * Tout;
+    {
+        float gmax = 0.f, nh = 0.f, nd = 1.f;
+        if (gstat) {
+            const int64_t g = group_size > 0 ? b / group_size : 0;
+            gmax = gstat[2 * g];
+            if (segment_norm) {
+                const float mn = fmaxf(gstat[2 * g + 1] - gmax, -80.f);
+                nh = mn / 2.f; nd = fabsf(nh + 1e-10f);
+            }
+        }
+        const float* xin = feat + (b * F + f0) * (int64_t)Tin;
+        for (int i = tid; i < rows * RS0; i += 256) {
+            const int r = i / RS0, t = i - r * RS0 - pad;
+            float v = 0.f;                          // conv zero padding (of the NORMALISED features)
+            if (t >= 0 && t < Tin) {
+                v = xin[r * Tin + t];
+                if (gstat) {
+                    v = max_keep_nan(v - gmax, -80.f);
+                    if (segment_norm) v = (v - nh) / nd;
+                }
+            }
+            s_x[i] = v;
+        }
+    }
+    const float4 w0 = *(const float4*)(w3 + 0 * Cout + 4 * cg);
+    const float4 w1 = *(const float4*)(w3 + 1 * Cout + 4 * cg);
+    const float4 w2 = *(const float4*)(w3 + 2 * Cout + 4 * cg);
+    const float4 bb = *(const float4*)(bias + 4 * cg);
+    const int64_t out0 = ((b * F + f0) * (int64_t)Tout) * Cout;
+    const int wg_bytes = npos * Cout * 4;           // <= 32 rows x 64 frames x Cout floats
+    const __amdgpu_buffer_rsrc_t rsG = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gamma + ((int64_t)f0 * Tout) * Cout), 0, wg_bytes, 0x00020000);
+    const int step = pos_per_iter * Cout * 4;       // bytes between a thread's consecutive positions
+    // a thread's positions are pslot + k * pos_per_iter, k = 0, 1, ...: (row, frame) advance by (d_r, d_to) with one wrap
+    const int d_r = pos_per_iter / Tout, d_to = pos_per_iter - d_r * Tout;
+    const int d_xo = d_r * RS0 + d_to * stride, wrap_xo = RS0 - Tout * stride;
+    int to = pslot % Tout;
+    int xo = (pslot / Tout) * RS0 + to * stride;    // LDS index of tap 0 (the staged row starts `pad` frames early)
+    int voff = (pslot * Cout + 4 * cg) * 4;         // byte offset of the position inside the workgroup's part of gamma / y
+    float* yw = y + out0 + pslot * Cout + 4 * cg;   // ... and where its z goes
+    __syncthreads();
+    float s = 0.f, q = 0.f;
+    float4 g[NP], gn[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) g[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsG, voff, i * step, 0));
+#define NAFP_CONV0_POSITION(i_)                                                                \
+    {                                                                                          \
+        const float x0 = s_x[xo], x1 = s_x[xo + 1], x2 = s_x[xo + 2];                          \
+        float4 tq, v;                                                                          \
+        tq.x = fmaf(x2, w2.x, fmaf(x1, w1.x, fmaf(x0, w0.x, bb.x)));                           \
+        tq.y = fmaf(x2, w2.y, fmaf(x1, w1.y, fmaf(x0, w0.y, bb.y)));                           \
+        tq.z = fmaf(x2, w2.z, fmaf(x1, w1.z, fmaf(x0, w0.z, bb.z)));                           \
+        tq.w = fmaf(x2, w2.w, fmaf(x1, w1.w, fmaf(x0, w0.w, bb.w)));                           \
+        v.x = elu1(tq.x); v.y = elu1(tq.y); v.z = elu1(tq.z); v.w = elu1(tq.w);                \
+        s += (v.x + v.y) + (v.z + v.w);                                                        \
+        q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);                                \
+        const f4nt zz = {v.x * g[i_].x, v.y * g[i_].y, v.z * g[i_].z, v.w * g[i_].w};         \
+        __builtin_nontemporal_store(zz, (f4nt*)(yw + (i_) * (step / 4)));   /* nt, as conv0_kernel; see above for why not a buffer store */ \
+        to += d_to; xo += d_xo;                                                                \
+        if (to >= Tout) { to -= Tout; xo += wrap_xo; }                                         \
+    }
+    const int n_full = npos / (NP * pos_per_iter);  // batches in which every thread's NP positions exist
+    // One batch: the gamma loads of the next batch first -- held there by the scheduling barrier: hipcc otherwise sinks them
+    // behind the stores, half a batch in front of their use --, then NP positions.
+#define NAFP_CONV0_BATCH()                                                                     \
+    {                                                                                          \
+        _Pragma("unroll") for (int i = 0; i < NP; ++i)                                         \
+            gn[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsG, voff + NP * step, i * step, 0)); \
+        NAFP_CONV0_SCHED_BARRIER                                                               \
+        _Pragma("unroll") for (int i = 0; i < NP; ++i) NAFP_CONV0_POSITION(i)                  \
+        voff += NP * step; yw += NP * (step / 4);                                              \
+        _Pragma("unroll") for (int i = 0; i < NP; ++i) g[i] = gn[i];                           \
+    }
+#define NAFP_CONV0_SCHED_BARRIER __builtin_amdgcn_sched_barrier(0);
+    // The first batch stands in front of the loop: at the loop's head the memory operations in flight are then the same
+    // on both ways in (NP loads, then NP stores), and the wait for the loads is a counted one that leaves the stores of
+    // the previous batch in flight.  (Entered straight from the first loads, the head has to assume nothing behind them
+    // and waits for everything.)
+    if (n_full > 0) {
+        NAFP_CONV0_BATCH()
+        for (int k = 1; k < n_full; ++k) NAFP_CONV0_BATCH()
+    }
+#undef NAFP_CONV0_BATCH
+#undef NAFP_CONV0_SCHED_BARRIER
+    if (n_full * NP * pos_per_iter < npos) {        // the ragged last batch
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            if (pslot + (n_full * NP + i) * pos_per_iter < npos) NAFP_CONV0_POSITION(i)
+        }
+    }
+#undef NAFP_CONV0_POSITION
+    double ds = wave_sum((double)s), dq = wave_sum((double)q);
+    if (lane == 0) { red[wave] = ds; red[4 + wave] = dq; }
+    __syncthreads();
+    if (tid == 0) {
+        stat_add(stats + 2 * b, red[0] + red[1] + red[2] + red[3], ident_stats != 0);
+        stat_add(stats + 2 * b + 1, red[4] + red[5] + red[6] + red[7], ident_stats != 0);
+    }
+}
+
 int launch_conv0(const float* feat, const float* w3, const float* bias, const float* gamma, float* y,
                  float* v_out, stat_t* stats, int64_t B, const ConvGeom& g, hipStream_t st, const float* gstat,
-                 int group_size, int segment_norm, bool ident_stats) {
+                 int group_size, int segment_norm, bool ident_stats, bool lean) {
     if (g.Cin != 1 || g.axis != 0 || (g.Cout % 4) != 0 || 256 % (g.Cout / 4) != 0 || g.Tin > 64) return NAFP_ERR_UNSUPPORTED;
     // rows per workgroup, measured at B = 640 on one box (ms): 4 -> 0.339, 8 -> 0.291, 16 -> 0.272 (the plain per-position
     // loop of round 1 ran 0.344; a store-only kernel of this shape 0.230: tools/probes/store_probe.hip)
     static const int rows = []() { const char* e = getenv("NAFP_CONV0_ROWS"); return e ? atoi(e) : 16; }();
-    if (rows == 4) {
+    if (lean && !v_out && rows == 16 && g.pad >= 0 && g.pad + g.Tin <= RS0 && (g.Tout - 1) * g.stride + 3 <= RS0) {
+        const int64_t blocks = B * ((g.Fin + 15) / 16);
+        conv0_lean_kernel<16><<<dim3((unsigned)blocks), 256, 0, st>>>(feat, w3, bias, gamma, y, stats, g.Fin, g.Tin, g.Tout, g.Cout, g.stride, g.pad,
+                                                                      gstat, group_size, segment_norm, ident_stats ? 1 : 0);
+    } else if (rows == 4) {
         const int64_t blocks = B * ((g.Fin + 3) / 4);
         conv0_kernel<true, 4><<<dim3((unsigned)blocks), 256, 0, st>>>(feat, w3, bias, gamma, y, v_out, stats, g.Fin, g.Tin, g.Tout,
                                                                     g.Cout, g.stride, g.pad, gstat, group_size, segment_norm, ident_stats ? 1 : 0);
@@ -360,6 +501,7 @@ struct ConvKernelParams {
     unsigned long long* tl;   // diagnostic phase timeline (nafp_conv_timeline), null in production: 8 u64 per wave
     int opt;                  // bit 0: the geometry prologue runs at raised wave priority, bit 1: the epilogue does (NAFP_GEMM_PRIO); bit 2: 3-D grid;
                               // bit 3: 1-D grid in XCD-aware order, bit 4: ... row-fastest (see the block-id decode of conv_gemm_body)
+    int keep_own;             // 1 (EPI 4 with two parts, NAFP_NONMATRIX_KEEP_OWN): the last arriver finishes on its own accumulators, see the epilogue
     // FUSE0 (conv1 only): the A operand z0 = gamma0 . ELU(conv0(feat)) is generated in-kernel
     // from the log-mel features instead of being read from memory (`x` unused).
     const float* f0_feat;     // (B, F0, T0)
@@ -1307,53 +1449,94 @@ __device__ __forceinline__ bool conv_gemm_body(const ConvKernelParams& p) {
         // its own included, from memory, in part order: the sum does not depend on who arrives last -- and runs the FULL
         // epilogue below on the total; the others leave.  One launch and one round trip of the output less per conv than
         // slab + finish kernel.
+        //
+        // Two parts (EPI 4, p.keep_own: NAFP_NONMATRIX_KEEP_OWN): the last arriver keeps its own part in its accumulators and adds the
+        // other one to them -- own + other has the bits of p0 + p1 whichever part it is (IEEE addition commutes; a partial sum is
+        // never -0).  A part has to know that it is last BEFORE it stores, so it draws a ticket first: 2 means that the other
+        // part has stored AND released (below), and this one goes straight on, with no store of its own and one part to read
+        // instead of two.  Any other value: the other part may still be on its way, nobody waits for anybody -- store, wait,
+        // barrier, then the release, a second add.  Of two parts that both took this way the one whose release returns 3 finds
+        // the other's part complete in memory and finishes, again on its own accumulators.  (adds: 0, 1 | 2 or 0, 1 | 2, 3.)
         const __amdgpu_buffer_rsrc_t rsP = __builtin_amdgcn_make_buffer_rsrc(
             p.y + ((int64_t)zsp * p.B + b0) * p.P * p.Cout, 0, (int)((unsigned)nb * (unsigned)ystep_b), 0x00020000);
+        // EPI 4: the lane offset of a 4-row group is formed where it is used, not kept -- held across the tickets next to the 64
+        // accumulators the eight offsets cost conv_gemm_n64k16s2_splitfin 56 B of scratch per lane, formed on demand 28 B, and the
+        // launch 125 -> 106 us (profiles/nonmatrix_ab.md).  EPI 5 (the backward pass) keeps them, as before.
+        auto form_voff = [&](int mi, int rg) {
+            const int grp = wm * 16 + mi * 8 + 2 * rg + (lane >> 5);
+            const int pos = sPos[grp >> (p.log2ST - 2)];
+            const int sl0 = (grp & (g4 - 1)) << 2;
+            return pos < p.P ? ((sl0 * p.P + pos) * p.Cout + n_base) * 4 : (int)0x80000000;
+        };
         int voffs[2][4];
+        if (EPI == 5) {
 #pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
+            for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-            for (int rg = 0; rg < 4; ++rg) {
-                const int grp = wm * 16 + mi * 8 + 2 * rg + (lane >> 5);
-                const int pos = sPos[grp >> (p.log2ST - 2)];
-                const int sl0 = (grp & (g4 - 1)) << 2;
-                voffs[mi][rg] = pos < p.P ? ((sl0 * p.P + pos) * p.Cout + n_base) * 4 : (int)0x80000000;
+                for (int rg = 0; rg < 4; ++rg) voffs[mi][rg] = form_voff(mi, rg);
+        }
+        auto voff_of = [&](int mi, int rg) { return EPI == 5 ? voffs[mi][rg] : form_voff(mi, rg); };
+        auto store_part = [&]() {
 #pragma unroll
-                for (int q = 0; q < 4; ++q)
+            for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-                    for (int ni = 0; ni < NIW; ++ni)
-                        __builtin_amdgcn_raw_buffer_store_b32(f2i(acc[mi][ni][rg * 4 + q]), rsP, voffs[mi][rg], q * ystep_b + ni * 128, 17);
-            }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // my part is in memory
-        __builtin_amdgcn_s_barrier();                                 // ... and so is every wave's of this workgroup
+                for (int rg = 0; rg < 4; ++rg) {
+                    const int voff = voff_of(mi, rg);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+#pragma unroll
+                        for (int ni = 0; ni < NIW; ++ni)
+                            __builtin_amdgcn_raw_buffer_store_b32(f2i(acc[mi][ni][rg * 4 + q]), rsP, voff, q * ystep_b + ni * 128, 17);
+                }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // my part is in memory
+            __builtin_amdgcn_s_barrier();                             // ... and so is every wave's of this workgroup
+        };
         unsigned* sTicket = (unsigned*)smem;
         const unsigned tile_id = (unsigned)((pb * p.n_sg + sg) * (p.Cout / BNT) + colz);
-        if (tid == 0) sTicket[0] = __hip_atomic_fetch_add(p.tickets + tile_id, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        const unsigned ticket = sTicket[0];
-        if (ticket != (unsigned)(p.n_split - 1)) return false;
+        const bool keep_own = EPI == 4 && p.keep_own;                 // (n_split == 2: launch_conv_gemm)
+        if (keep_own) {
+            __syncthreads();                                          // every wave has left the K-loop: the ring's first bytes are free
+            if (tid == 0) sTicket[0] = __hip_atomic_fetch_add(p.tickets + tile_id, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __syncthreads();
+            if (sTicket[0] != 2u) {
+                store_part();                                         // (its barrier: everybody has read sTicket)
+                if (tid == 0) sTicket[0] = __hip_atomic_fetch_add(p.tickets + tile_id, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __syncthreads();
+                if (sTicket[0] != 3u) return false;
+            }
+        } else {
+            store_part();
+            if (tid == 0) sTicket[0] = __hip_atomic_fetch_add(p.tickets + tile_id, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __syncthreads();
+            const unsigned ticket = sTicket[0];
+            if (ticket != (unsigned)(p.n_split - 1)) return false;
+        }
         __syncthreads();                                              // sTicket is read: LDS is reused by the statistics below
         if (tid == 0)                                                 // ready for the next launch; agent scope like every other access
             __hip_atomic_store(p.tickets + tile_id, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (!keep_own) {
 #pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
+            for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-            for (int ni = 0; ni < NIW; ++ni)
+                for (int ni = 0; ni < NIW; ++ni)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
-        for (int z = 0; z < p.n_split; ++z) {
+                    for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+        }
+        for (int z = keep_own ? 1 - zsp : 0; z < (keep_own ? 2 - zsp : p.n_split); ++z) {     // keep_own: the other part alone
             const __amdgpu_buffer_rsrc_t rsZ = __builtin_amdgcn_make_buffer_rsrc(
                 p.y + ((int64_t)z * p.B + b0) * p.P * p.Cout, 0, (int)((unsigned)nb * (unsigned)ystep_b), 0x00020000);
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-                for (int rg = 0; rg < 4; ++rg)
+                for (int rg = 0; rg < 4; ++rg) {
+                    const int voff = voff_of(mi, rg);
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
 #pragma unroll
                         for (int ni = 0; ni < NIW; ++ni)
                             acc[mi][ni][rg * 4 + q] += __builtin_bit_cast(
-                                float, __builtin_amdgcn_raw_buffer_load_b32(rsZ, voffs[mi][rg], q * ystep_b + ni * 128, 17));
+                                float, __builtin_amdgcn_raw_buffer_load_b32(rsZ, voff, q * ystep_b + ni * 128, 17));
+                }
         }
         if (EPI == 5) {
             float bv[NIW];
@@ -1371,7 +1554,7 @@ __device__ __forceinline__ bool conv_gemm_body(const ConvKernelParams& p) {
                     for (int q = 0; q < 4; ++q)
 #pragma unroll
                         for (int ni = 0; ni < NIW; ++ni)
-                            __builtin_amdgcn_raw_buffer_store_b32(f2i(acc[mi][ni][rg * 4 + q] + bv[ni]), rsF, voffs[mi][rg], q * ystep_b + ni * 128, 0);
+                            __builtin_amdgcn_raw_buffer_store_b32(f2i(acc[mi][ni][rg * 4 + q] + bv[ni]), rsF, voff_of(mi, rg), q * ystep_b + ni * 128, 0);
             return false;
         }
     }
@@ -1831,6 +2014,7 @@ int launch_conv_gemm(const ConvGemmArgs& a, int64_t B, const ConvGeom& g, hipStr
     // a split launch writes its parts to the slab; the bias is added where the parts meet
     if (pl.S > 1) { p.y = a.slab; p.bias = pl.finish == CONV_FINISH_IN_KERNEL_PLAIN ? a.bias : nullptr; }
     p.tickets = in_kernel ? a.tickets : nullptr; p.y_final = a.y;
+    p.keep_own = (a.nonmatrix & NAFP_NONMATRIX_KEEP_OWN) && pl.finish == CONV_FINISH_IN_KERNEL_FULL && pl.S == 2;
     p.f0_feat = nullptr; p.f0_w = nullptr; p.f0_bias = nullptr; p.f0_gamma = nullptr;
     p.f0_T = 0; p.f0_stride = 1; p.f0_pad = 0; p.f0_gstat = nullptr; p.f0_group = 0; p.f0_segnorm = 0;
     if (a.f0_feat) {
@@ -2155,7 +2339,7 @@ int launch_dgrad_ln(const DgradLnArgs& a, int64_t B, const ConvGeom& g, hipStrea
     p.sample_in = (int64_t)g.Fout * g.Tout * g.Cout;
     const int S = g.axis == 0 ? g.Cout : g.Tout * g.Cout;
     p.tap_stride = -(S / g.stride);
-    p.inv_n_in = 1.0; p.mode = 1; p.n_split = 1; p.abl = 0; p.tl = nullptr; p.opt = 0; p.tickets = nullptr; p.y_final = nullptr;
+    p.inv_n_in = 1.0; p.mode = 1; p.n_split = 1; p.abl = 0; p.tl = nullptr; p.opt = 0; p.tickets = nullptr; p.y_final = nullptr; p.keep_own = 0;
     p.sj = ScalarsJob{nullptr, nullptr, nullptr, nullptr, 0, 0.0};
     p.perm_on = 0; p.perm_n0 = 0; p.perm_c0 = 0;        // one position per workgroup: no class ordering needed
     p.wp_bytes = (unsigned)((int64_t)g.Cout * 3 * g.Cin * 4);

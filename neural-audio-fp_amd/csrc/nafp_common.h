@@ -157,7 +157,8 @@ __device__ __forceinline__ void atomic_min_float(float* addr, float v) {
 // subtraction / clamp / segment normalisation of melspectrogram.py:108-111 is applied on load.
 int launch_conv0(const float* feat, const float* w3, const float* bias, const float* gamma, float* y,
                  float* v_out, stat_t* stats, int64_t B, const ConvGeom& g, hipStream_t st,
-                 const float* gstat = nullptr, int group_size = 0, int segment_norm = 0, bool ident_stats = false);
+                 const float* gstat = nullptr, int group_size = 0, int segment_norm = 0, bool ident_stats = false,
+                 bool lean = false);       // lean: the straight-line form of the kernel (NAFP_NONMATRIX_CONV0), same bytes
 
 // implicit-GEMM conv (see conv.hip for the LayerNorm folding).
 constexpr int NAFP_TICKET_SLOTS = 4096;      // output tiles of a split-K launch that finishes in-kernel
@@ -192,6 +193,7 @@ struct ConvGemmArgs {
     const ScalarsJob* sj;    // optional (PLAIN launches of the backward pass): side job, see ScalarsJob
     int64_t plan_b;          // > 0 (inference forward): take the tile shape and the split-K factor the launch would have at THIS batch size,
                              // whatever B is -- the fp32 summation order of a segment then does not depend on the launch size (see fwd_plan_b())
+    int nonmatrix;           // NAFP_NONMATRIX_* bits (include/nafp.h) that concern this launch: KEEP_OWN
 };
 // statistics (sum, sum of squares of ELU(conv0 + bias) per sample) without storing the activation
 int launch_conv0_stats(const float* feat, const float* w3, const float* bias, stat_t* stats, int64_t B,

@@ -210,6 +210,10 @@ int nafp_resample_i16(nafp_resample* plan, const int16_t* raw, int64_t raw_sampl
  *   NAFP_INGEST_F32 / NAFP_INGEST_F64  IEEE   NaN -> 0; otherwise q = clamp(rint(x * 2^23), -2^23, 2^23 - 1), ties to even, the
  *                                             clamp applied before the conversion to integer (infinities clamp, denormals give
  *                                             0); computed from the bit pattern in integers on host and device alike
+ *   NAFP_INGEST_S8   signed 8-bit PCM         q = x << 16   (AIFF and AU hold 8-bit samples signed)
+ *   NAFP_INGEST_BE   a flag on S16, S24, S32, F32 and F64 only (the codes 18 .. 22): the sample's bytes stand in the opposite
+ *                    order, as AIFF / AIFF-C and AU hold them; q is the little-endian rule applied to the reversed bytes.
+ * Every other value -- 0, 7, 9 .. 17, 23 and above, the flag on U8 or S8 -- is NAFP_ERR_UNSUPPORTED from every entry point.
  * Down-mix: m[j] = sum_c q[j][c] over the C = 1..8 channels of frame j, equal weights; the division by C is part of the
  * final rounding.
  * Ratio: g = gcd(fs_in, fs_out), L = fs_out / g, M = fs_in / g.  Supported: both rates <= 192000 and L <= 640, in either
@@ -235,6 +239,8 @@ typedef struct nafp_ingest nafp_ingest;
 #define NAFP_INGEST_S32 4
 #define NAFP_INGEST_F32 5
 #define NAFP_INGEST_F64 6
+#define NAFP_INGEST_S8 8
+#define NAFP_INGEST_BE 16 /* a flag: NAFP_INGEST_S16 .. NAFP_INGEST_F64 | NAFP_INGEST_BE, the codes 18 .. 22 */
 
 /* A run of consecutive output samples of one file: nafp_resample_piece with a BYTE offset into a uint8 arena (any
  * alignment), a format code and 1..8 channels.  64 bytes. */
@@ -335,8 +341,9 @@ int nafp_varispeed_i16(nafp_varispeed* plan, const int16_t* src, int64_t src_sam
                        int64_t n_pieces, int16_t* out, int64_t out_samples, void* stream);
 
 /* ------------------------------------------------------------------------
- * Block codecs in RIFF/WAVE: G.711 A-law and mu-law, IMA ADPCM and MS ADPCM at 4 bits (csrc/codec.hip, the arithmetic in
- * csrc/codec_decode.h; numpy restatement tests/_codec_ref.py).  A PRE-PASS of nafp_ingest_*, which is
+ * Block codecs in RIFF/WAVE: G.711 A-law and mu-law, IMA ADPCM and MS ADPCM at 4 bits, and Apple's IMA4 packets of AIFF-C
+ * (csrc/codec.hip, the arithmetic in csrc/codec_decode.h; numpy restatements tests/_codec_ref.py and tests/_aiff_ref.py;
+ * DESIGN.md sections 4.10.2 and 4.10.5).  A PRE-PASS of nafp_ingest_*, which is
  * unchanged: whole blocks are decoded to interleaved 16-bit PCM in a device arena, which nafp_ingest_i16 then reads as
  * NAFP_INGEST_S16.  A "block" is block_align bytes and yields spb (samples per block) frames of C = channels interleaved int16.
  * ALL ARITHMETIC IS int32 AND EXACT: a decoded sample is a pure function of (its block's bytes, its place in the block),
@@ -364,6 +371,13 @@ int nafp_varispeed_i16(nafp_varispeed* plan, const int16_t* src, int64_t src_sam
  *     delta = clamp((ADAPT[n] delta) >> 8, 16, 2796202), arithmetic shift (2796202 = INT_MAX / 768: every product fits int32);
  *   ADAPT = {230,230,230,230,307,409,512,614,768,614,512,409,307,230,230,230}.  The header's iDelta, sign-extended, is used as
  *   it stands for the first nibble.
+ * Apple IMA4 (the `ima4` compression of AIFF-C; NAFP_CODEC_QT_IMA4) -- C = 1 or 2; block_align = 34 C, spb = 64.
+ *   Layout: one 34-byte packet per channel, channel c's at bytes [34 c, 34 c + 34).  A packet is a BIG-endian uint16 h --
+ *   predictor = (int16)(h & 0xFF80), step index = min(h & 0x7F, 88) -- and 32 bytes of two nibbles each, LOW nibble first, every
+ *   nibble through the IMA recurrence above.  The 64 predictor values AFTER each nibble are frames 0 .. 63 of the channel; the
+ *   header's predictor itself is not a sample.  The decode is STATELESS PER PACKET, as the contract of this section requires: no
+ *   state is carried from the packet before (decoders that carry it when it agrees with the header to within the 7 dropped
+ *   bits, or that form the step product by a multiplication, differ in the low bits).
  * Status: a codec, channel count or block_align outside the lists NAFP_ERR_UNSUPPORTED, null pointers / negative sizes / an
  * inconsistent piece NAFP_ERR_INVALID_ARG, all before any GPU call.
  * ---------------------------------------------------------------------- */
@@ -371,6 +385,7 @@ int nafp_varispeed_i16(nafp_varispeed* plan, const int16_t* src, int64_t src_sam
 #define NAFP_CODEC_ULAW 2
 #define NAFP_CODEC_IMA4 3
 #define NAFP_CODEC_MS4 4
+#define NAFP_CODEC_QT_IMA4 6 /* 5 is not a codec */
 
 /* A run of whole blocks of one file.  40 bytes. */
 typedef struct nafp_codec_piece {

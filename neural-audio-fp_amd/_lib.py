@@ -216,7 +216,8 @@ RESAMPLE_PIECE_DTYPE = [('raw_off', '<i8'), ('frame0', '<i8'), ('n_frames', '<i8
 INGEST_PIECE_DTYPE = [('raw_off', '<i8'), ('frame0', '<i8'), ('n_frames', '<i8'), ('n_in', '<i8'), ('out0', '<i8'),
                       ('out_off', '<i8'), ('n_out', '<i4'), ('channels', '<i4'), ('format', '<i4'), ('reserved', '<i4')]
 # NAFP_INGEST_* format codes (include/nafp.h): name -> (code, bytes per sample)
-INGEST_FORMATS = {'u8': (1, 1), 's16': (2, 2), 's24': (3, 3), 's32': (4, 4), 'f32': (5, 4), 'f64': (6, 8)}
+INGEST_FORMATS = {'u8': (1, 1), 's16': (2, 2), 's24': (3, 3), 's32': (4, 4), 'f32': (5, 4), 'f64': (6, 8), 's8': (8, 1),
+                  's16be': (18, 2), 's24be': (19, 3), 's32be': (20, 4), 'f32be': (21, 4), 'f64be': (22, 8)}      # NAFP_INGEST_BE = 16
 
 # nafp_varispeed_piece (include/nafp.h) as a numpy structured dtype: 56 bytes per piece
 VARISPEED_PIECE_DTYPE = [('src_off', '<i8'), ('frame0', '<i8'), ('n_frames', '<i8'), ('n_in', '<i8'), ('out0', '<i8'),
@@ -226,8 +227,8 @@ VARISPEED_STEP_MIN, VARISPEED_STEP_MAX = 13421773, 20971520      # NAFP_VARISPEE
 # nafp_codec_piece (include/nafp.h) as a numpy structured dtype: 40 bytes per piece; raw_off counts BYTES, out_off int16
 CODEC_PIECE_DTYPE = [('raw_off', '<i8'), ('n_blocks', '<i8'), ('out_off', '<i8'), ('codec', '<i4'), ('channels', '<i4'),
                      ('block_align', '<i4'), ('spb', '<i4')]
-# NAFP_CODEC_* codes (include/nafp.h): the `format` name riff_scan_ex gives such a file -> code
-CODECS = {'alaw': 1, 'ulaw': 2, 'ima4': 3, 'ms4': 4}
+# NAFP_CODEC_* codes (include/nafp.h): the `format` name riff_scan_ex / aiff_scan / au_scan give such a file -> code
+CODECS = {'alaw': 1, 'ulaw': 2, 'ima4': 3, 'ms4': 4, 'qtima4': 6}
 
 # nafp_flac_info / nafp_flac_index_entry / nafp_flac_frame (include/nafp.h) as numpy structured dtypes: 72 / 32 / 40 bytes
 FLAC_INFO_DTYPE = [('total_samples', '<i8'), ('audio_off', '<i8'), ('n_indexed', '<i8'), ('indexed_samples', '<i8'), ('rate', '<i4'),

@@ -1,5 +1,5 @@
-// Block codecs of RIFF/WAVE -- G.711 A-law / mu-law, IMA ADPCM and MS ADPCM at 4 bits -- decoded to interleaved int16 PCM, gfx950.
-// A pre-pass of the ingest (ingest.hip, unchanged), which reads this kernel's output arena as NAFP_INGEST_S16.
+// Block codecs of RIFF/WAVE -- G.711 A-law / mu-law, IMA ADPCM and MS ADPCM at 4 bits -- and Apple's IMA4 packets of AIFF-C, decoded
+// to interleaved int16 PCM, gfx950.  A pre-pass of the ingest (ingest.hip), which reads this kernel's output arena as NAFP_INGEST_S16.
 //
 // Contract (include/nafp.h has it in full; the arithmetic is csrc/codec_decode.h, shared with the host): int32 throughout, a
 // decoded sample is a pure function of (its block's bytes, its place in the block).
@@ -26,6 +26,8 @@
 //   as many blocks as that holds, both images counted, at most 256 lanes -- 64 blocks at block_align 256 mono, 16 at 1024
 //   stereo, 4 at 4096 mono.  Measured against 64 KB (more rounds), 160 KB (one workgroup per compute unit: no fewer rounds for
 //   the blocks of a launch, slower nibbles) and one-wave workgroups of 20 KB (8 decoding waves per compute unit share its SIMDs).
+//   Apple IMA4 runs in the same kernel on a path of its own (cd_qt_piece): 34-byte packets of 64 nibbles, where staging and
+//   stores set the time and not the recurrence.
 #include "nafp_common.h"
 
 #include "codec_decode.h"
@@ -35,6 +37,10 @@ namespace nafp {
 constexpr int CD_THREADS = 256;
 constexpr int CD_LDS_BYTES = 80 * 1024;                // half the LDS of a gfx950 compute unit: two workgroups on each
 constexpr int CD_G711_STEP = CD_THREADS * 8;          // samples per workgroup step
+constexpr int CD_QT_LANES = 256;                      // Apple IMA4: (block, channel) lanes per group, chosen by measurement
+constexpr int CD_QT_IN_BYTES = CD_QT_LANES * CD_QT_PACKET + 16;      // a group's packets and the skew of their first byte; 16 | it
+static_assert(CD_QT_LANES <= CD_THREADS && CD_QT_IN_BYTES % 16 == 0 && CD_QT_IN_BYTES + CD_QT_LANES * (CD_QT_SPB * 2 + 4) <= CD_LDS_BYTES,
+              "Apple IMA4 group in LDS");
 
 struct CdGroup { int in_dw, out_dw, blocks; };
 
@@ -117,6 +123,24 @@ __device__ __forceinline__ void cd_g711_piece(const nafp_codec_piece& pc, const 
     }
 }
 
+// the group's output image, nb rows of row_len int16 at a stride of out_dw dwords -> n_el consecutive int16 of the arena at dst,
+// inside it (cd_piece_fault): coalesced 4-byte stores, 2-byte ones for an odd first or last sample
+__device__ __forceinline__ void cd_store_image(int16_t* __restrict__ dst, const uint16_t* so, int nb, int row_len, int out_dw, int tid) {
+    const int n_el = nb * row_len;
+    const int head = (int)(((uintptr_t)dst >> 1) & 1);
+    const int n_pair = (n_el - head) / 2;
+    for (int k = tid; k < n_pair; k += CD_THREADS) {
+        const int e = head + 2 * k;
+        int r = e / row_len, c0 = e - r * row_len;
+        const uint32_t lo = so[r * out_dw * 2 + c0];
+        if (++c0 == row_len) { c0 = 0; ++r; }
+        const uint32_t hi = so[r * out_dw * 2 + c0];
+        *(uint32_t*)(dst + e) = lo | (hi << 16);
+    }
+    if (tid == 0 && head) dst[0] = (int16_t)so[0];
+    if (tid == 1 && ((n_el - head) & 1)) dst[n_el - 1] = (int16_t)so[(nb - 1) * out_dw * 2 + row_len - 1];
+}
+
 __device__ __forceinline__ void cd_adpcm_piece(const nafp_codec_piece& pc, const uint8_t* __restrict__ raw, int16_t* __restrict__ out,
                                                uint32_t* s_lds, int tid) {
     const int C = pc.channels, align = pc.block_align, spb = pc.spb, codec = pc.codec;
@@ -137,25 +161,60 @@ __device__ __forceinline__ void cd_adpcm_piece(const nafp_codec_piece& pc, const
             const int blk = tid / C, c = tid - blk * C;
             const CdLdsReader rd{s_in + blk * g.in_dw};
             const CdLdsWriter wr{(int16_t*)(s_out + blk * g.out_dw), C};
-            cd_block_channel(codec, C, align, c, rd, wr);
+            if (codec == NAFP_CODEC_IMA4) cd_ima_channel(C, align, c, rd, wr);
+            else cd_ms_channel(C, align, c, rd, wr);
         }
         __syncthreads();
-        // the group's output: n_el consecutive int16 of the arena, inside it (cd_piece_fault)
-        int16_t* dst = out + pc.out_off + b0 * row_len;
-        const uint16_t* so = (const uint16_t*)s_out;
-        const int n_el = nb * row_len;
-        const int head = (int)(((uintptr_t)dst >> 1) & 1);
-        const int n_pair = (n_el - head) / 2;
-        for (int k = tid; k < n_pair; k += CD_THREADS) {
-            const int e = head + 2 * k;
-            int r = e / row_len, c0 = e - r * row_len;
-            const uint32_t lo = so[r * g.out_dw * 2 + c0];
-            if (++c0 == row_len) { c0 = 0; ++r; }
-            const uint32_t hi = so[r * g.out_dw * 2 + c0];
-            *(uint32_t*)(dst + e) = lo | (hi << 16);
+        cd_store_image(out + pc.out_off + b0 * row_len, (const uint16_t*)s_out, nb, row_len, g.out_dw, tid);
+        // the next round's staging writes s_in only, last read before the barrier above; s_out is next written after a barrier
+    }
+}
+
+// n_bytes at src (any alignment) -> s_bytes + (src & 15), so that every 16-byte unit of global memory is a 16-byte unit of
+// LDS: 16-byte loads over the aligned middle of the range, single bytes for the up to 15 before and after it.  Nothing outside
+// [src, src + n_bytes) is read.  Returns the skew (src & 15); s_bytes is 16-byte aligned and holds n_bytes + 15.
+__device__ __forceinline__ int cd_stage_linear(const uint8_t* __restrict__ src, int n_bytes, uint8_t* s_bytes, int tid) {
+    const int skew = (int)((uintptr_t)src & 15);
+    int head = skew ? 16 - skew : 0;
+    if (head > n_bytes) head = n_bytes;
+    const int n_vec = (n_bytes - head) / 16;
+    for (int i = tid; i < n_vec; i += CD_THREADS) *(uint4*)(s_bytes + skew + head + 16 * i) = *(const uint4*)(src + head + 16 * i);
+    const int tail = head + 16 * n_vec;                                // < 31 single bytes in all
+    if (tid < head) s_bytes[skew + tid] = src[tid];
+    else if (tid >= 32 && tid - 32 < n_bytes - tail) s_bytes[skew + tail + tid - 32] = src[tail + tid - 32];
+    return skew;
+}
+
+struct CdLdsByteReader {
+    const uint8_t* p;
+    __device__ __forceinline__ uint32_t u8(int i) const { return p[i]; }
+};
+
+// Apple IMA4: a block is 34 C bytes -- 2-byte aligned at best, so the row staging above would go byte by byte -- and only 64
+// nibbles per lane, so what a group costs is its staging and its stores, not the recurrence.  The group's byte range is staged as
+// it stands (cd_stage_linear: 16-byte loads whatever the block stride), the lanes read their packets at a stride of 34 bytes (8.5
+// dwords: the 64 lanes of a wave fall on different banks but for pairs that share a dword) and the output image and its stores are
+// the ones above.  CD_QT_LANES lanes per group: 256 / C blocks, 8.7 KB in and 33.8 KB out.
+__device__ __forceinline__ void cd_qt_piece(const nafp_codec_piece& pc, const uint8_t* __restrict__ raw, int16_t* __restrict__ out,
+                                            uint32_t* s_lds, int tid) {
+    const int C = pc.channels, align = CD_QT_PACKET * C, row_len = CD_QT_SPB * C;      // as cd_piece_fault found them
+    const int blocks = CD_QT_LANES / C, out_dw = (row_len / 2) | 1;
+    uint8_t* s_in = (uint8_t*)s_lds;
+    uint32_t* s_out = s_lds + CD_QT_IN_BYTES / 4;
+    const uint8_t* base = raw + pc.raw_off;
+    for (int64_t b0 = (int64_t)blockIdx.x * blocks; b0 < pc.n_blocks; b0 += (int64_t)gridDim.x * blocks) {
+        const int nb = (int)(pc.n_blocks - b0 < blocks ? pc.n_blocks - b0 : blocks);
+        // [0, nb * align) at src is inside the raw arena (cd_piece_fault); nb * align <= CD_QT_LANES * 34
+        const int skew = cd_stage_linear(base + b0 * align, nb * align, s_in, tid);
+        __syncthreads();
+        if (tid < nb * C) {
+            const int blk = tid / C, c = tid - blk * C;
+            const CdLdsByteReader rd{s_in + skew + blk * align};
+            const CdLdsWriter wr{(int16_t*)(s_out + blk * out_dw), C};
+            cd_qt_channel(c, rd, wr);
         }
-        if (tid == 0 && head) dst[0] = (int16_t)so[0];
-        if (tid == 1 && ((n_el - head) & 1)) dst[n_el - 1] = (int16_t)so[(nb - 1) * g.out_dw * 2 + row_len - 1];
+        __syncthreads();
+        cd_store_image(out + pc.out_off + b0 * row_len, (const uint16_t*)s_out, nb, row_len, out_dw, tid);
         // the next round's staging writes s_in only, last read before the barrier above; s_out is next written after a barrier
     }
 }
@@ -183,6 +242,7 @@ __global__ __launch_bounds__(CD_THREADS) void codec_adpcm_kernel(const uint8_t* 
     const nafp_codec_piece pc = pieces[blockIdx.y];
     if (cd_piece_fault(pc, raw_size, out_samples) != 0) return;        // codec_g711_kernel deals with it
     if (pc.codec == NAFP_CODEC_IMA4 || pc.codec == NAFP_CODEC_MS4) cd_adpcm_piece(pc, raw, out, s_lds, threadIdx.x);
+    else if (pc.codec == NAFP_CODEC_QT_IMA4) cd_qt_piece(pc, raw, out, s_lds, threadIdx.x);
 }
 
 }  // namespace nafp
@@ -197,6 +257,7 @@ extern "C" int nafp_codec_blocks_per_group(int codec, int channels, int block_al
     const int spb = cd_samples_per_block(codec, channels, block_align);
     if (spb < 0) return -1;
     if (codec == NAFP_CODEC_ALAW || codec == NAFP_CODEC_ULAW) return CD_G711_STEP / channels;
+    if (codec == NAFP_CODEC_QT_IMA4) return CD_QT_LANES / channels;
     return cd_group(channels, block_align, spb).blocks;
 }
 

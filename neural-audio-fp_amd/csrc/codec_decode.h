@@ -1,9 +1,9 @@
-// Per-sample and per-block arithmetic of the block codecs (include/nafp.h `nafp_codec_*`): G.711 A-law and
-// mu-law, IMA ADPCM and MS ADPCM at 4 bits.  Plain C++ in int32, no table for G.711, no 16-bit arithmetic.  ONE definition for
-// the kernel (csrc/codec.hip), the host entry point nafp_codec_decode_host and any stand-alone host program: every function is
-// NAFP_CODEC_HD, which is `__host__ __device__` under hipcc and nothing elsewhere.  A block is read through `rd` (u8(i): byte i
-// of the block; u32(i): the little-endian dword at byte i, i a multiple of 4) and written through `wr(frame, channel, x)`, so
-// the kernel can keep both in LDS and the host in plain arrays.
+// Per-sample and per-block arithmetic of the block codecs (include/nafp.h `nafp_codec_*`, DESIGN.md sections 4.10.2 and 4.10.5):
+// G.711 A-law and mu-law, IMA ADPCM and MS ADPCM at 4 bits, Apple IMA4 packets.  Plain C++ in int32, no table for G.711, no 16-bit
+// arithmetic.  ONE definition for the kernel (csrc/codec.hip), the host entry point nafp_codec_decode_host and any stand-alone
+// host program: every function is NAFP_CODEC_HD, which is `__host__ __device__` under hipcc and nothing elsewhere.  A block is
+// read through `rd` (u8(i): byte i of the block; u32(i): the little-endian dword at byte i, i a multiple of 4) and written through
+// `wr(frame, channel, x)`, so the kernel can keep both in LDS and the host in plain arrays.
 #ifndef NAFP_CODEC_DECODE_H
 #define NAFP_CODEC_DECODE_H
 
@@ -22,6 +22,8 @@ namespace nafp {
 constexpr int CD_MAX_ALIGN = 4096;
 constexpr int CD_MAX_G711_CHANNELS = 8;
 constexpr int CD_MAX_SPB = 8185;                       // IMA mono at block_align 4096: 8 * 1023 + 1
+constexpr int CD_QT_PACKET = 34;                       // Apple IMA4: a 2-byte header and 32 bytes of nibbles per channel
+constexpr int CD_QT_SPB = 64;
 
 NAFP_CODEC_HD int32_t cd_clamp16(int32_t x) { return x < -32768 ? -32768 : (x > 32767 ? 32767 : x); }
 
@@ -42,6 +44,8 @@ NAFP_CODEC_HD int cd_samples_per_block(int codec, int channels, int block_align)
             if (channels > 2 || block_align <= 7 * channels) return -1;
             return 2 + 2 * (block_align - 7 * channels) / channels;      // 2 (align - 7 C) is a multiple of C for C = 1, 2
         }
+        case NAFP_CODEC_QT_IMA4:
+            return channels <= 2 && block_align == CD_QT_PACKET * channels ? CD_QT_SPB : -1;
     }
     return -1;
 }
@@ -156,11 +160,30 @@ NAFP_CODEC_HD void cd_ms_channel(int channels, int block_align, int c, const Rd&
     }
 }
 
-// channel c of one block of any of the four codecs (the geometry is taken as checked: cd_samples_per_block > 0)
+// channel c of one Apple IMA4 block: its packet at byte 34 c.  The header is big-endian and keeps the predictor's upper 9 bits;
+// the predictor AFTER each nibble is a frame, the header's own value is none.  Nothing comes from the packet before.
+template <class Rd, class Wr>
+NAFP_CODEC_HD void cd_qt_channel(int c, const Rd& rd, const Wr& wr) {
+    const int at = CD_QT_PACKET * c;
+    const uint32_t h = (rd.u8(at) << 8) | rd.u8(at + 1);
+    int32_t pred = (int32_t)(int16_t)(uint16_t)(h & 0xff80u);
+    int32_t idx = (int32_t)(h & 0x7fu);
+    if (idx > 88) idx = 88;
+    for (int i = 0; i < 32; ++i) {
+        const uint32_t b = rd.u8(at + 2 + i);
+        cd_ima_nibble((int32_t)(b & 15u), pred, idx);
+        wr(2 * i, c, pred);
+        cd_ima_nibble((int32_t)(b >> 4), pred, idx);
+        wr(2 * i + 1, c, pred);
+    }
+}
+
+// channel c of one block of any of the codecs (the geometry is taken as checked: cd_samples_per_block > 0)
 template <class Rd, class Wr>
 NAFP_CODEC_HD void cd_block_channel(int codec, int channels, int block_align, int c, const Rd& rd, const Wr& wr) {
     if (codec == NAFP_CODEC_IMA4) cd_ima_channel(channels, block_align, c, rd, wr);
     else if (codec == NAFP_CODEC_MS4) cd_ms_channel(channels, block_align, c, rd, wr);
+    else if (codec == NAFP_CODEC_QT_IMA4) cd_qt_channel(c, rd, wr);
     else wr(0, c, cd_g711(codec, rd.u8(c)));
 }
 

@@ -1,5 +1,6 @@
-// Ingest of RIFF/WAVE sample data of any PCM or IEEE-float format, 1 to 8 channels, at any supported rate -- up OR down -- to
-// int16 mono at the model rate, gfx950.  The general sibling of resample.hip (16-bit, 1 or 2 channels, downsampling), which
+// Ingest of sample data of any PCM or IEEE-float format -- little-endian as RIFF/WAVE holds it, or big-endian and signed 8-bit as
+// AIFF / AIFF-C and AU do (NAFP_INGEST_BE, NAFP_INGEST_S8) -- 1 to 8 channels, at any supported rate -- up OR down -- to int16 mono at
+// the model rate, gfx950.  The general sibling of resample.hip (16-bit, 1 or 2 channels, downsampling), which
 // stays as it is; for the files both take, the bytes are the same.
 //
 // Contract (include/nafp.h has it in full): every sample is first DECODED to the canonical q, a signed integer at 2^-23 of
@@ -14,7 +15,8 @@
 // The kernel is resample_i16_kernel's: one workgroup per 256 consecutive outputs of one piece, the block's input span decoded
 // and down-mixed into LDS as int32 once, every lane walking the taps of its phase in the [tap][phase] table.  What differs: the
 // raw arena is BYTES (a 24-bit 3-channel frame is 9 of them, at any alignment): a sample is loaded as one naturally aligned
-// unit where the piece's first byte is aligned to the sample size and byte by byte otherwise, never wider than its alignment;
+// unit where the piece's first byte is aligned to the sample size and byte by byte otherwise, never wider than its alignment (a
+// big-endian sample is that one load byte-swapped, or its bytes assembled the other way round: uniform per piece);
 // the finish divides by D (a shift by 38 and one 32-bit floor division by the channel count, which is the same number);
 // L goes up to 640.
 #include <math.h>
@@ -104,14 +106,21 @@ __host__ __device__ inline void ig_input_range(int64_t n0, int64_t n1, int64_t n
 // bytes of one sample of a format code; 0: not a format
 __host__ __device__ inline int ig_sample_bytes(int format) {
     switch (format) {
-        case NAFP_INGEST_U8: return 1;
-        case NAFP_INGEST_S16: return 2;
-        case NAFP_INGEST_S24: return 3;
-        case NAFP_INGEST_S32: return 4;
-        case NAFP_INGEST_F32: return 4;
-        case NAFP_INGEST_F64: return 8;
+        case NAFP_INGEST_U8: case NAFP_INGEST_S8: return 1;
+        case NAFP_INGEST_S16: case NAFP_INGEST_S16 | NAFP_INGEST_BE: return 2;
+        case NAFP_INGEST_S24: case NAFP_INGEST_S24 | NAFP_INGEST_BE: return 3;
+        case NAFP_INGEST_S32: case NAFP_INGEST_S32 | NAFP_INGEST_BE: return 4;
+        case NAFP_INGEST_F32: case NAFP_INGEST_F32 | NAFP_INGEST_BE: return 4;
+        case NAFP_INGEST_F64: case NAFP_INGEST_F64 | NAFP_INGEST_BE: return 8;
     }
     return 0;
+}
+
+// the `bytes` low bytes of u in the opposite order
+__host__ __device__ inline uint64_t ig_reverse(uint64_t u, int bytes) {
+    uint64_t r = 0;
+    for (int b = 0; b < bytes; ++b, u >>= 8) r = (r << 8) | (u & 0xff);
+    return r;
 }
 
 // clamp(rint(x * 2^23), -2^23, 2^23 - 1) of the IEEE value with sign `neg`, biased exponent `e` (bias `bias`, all-ones `emax`) and
@@ -131,10 +140,11 @@ __host__ __device__ inline int32_t ig_float_q(bool neg, int e, uint64_t man, int
     return k > 8388607 ? 8388607 : (int32_t)k;
 }
 
-// the canonical sample from the little-endian value `u` of its ig_sample_bytes(format) bytes
-__host__ __device__ inline int32_t ig_decode(int format, uint64_t u) {
+// the canonical sample from the little-endian value `u` of the bytes of a little-endian format code (or NAFP_INGEST_S8)
+__host__ __device__ inline int32_t ig_decode_le(int format, uint64_t u) {
     switch (format) {
         case NAFP_INGEST_U8: return ((int32_t)(u & 0xff) - 128) * 65536;
+        case NAFP_INGEST_S8: return (int32_t)(int8_t)(uint8_t)u * 65536;
         case NAFP_INGEST_S16: return (int32_t)(int16_t)(uint16_t)u * 256;
         case NAFP_INGEST_S24: return (int32_t)((uint32_t)u << 8) >> 8;
         case NAFP_INGEST_S32: {
@@ -149,6 +159,14 @@ __host__ __device__ inline int32_t ig_decode(int format, uint64_t u) {
             return ig_float_q((u >> 63) != 0, (int)((u >> 52) & 0x7ff), u & (((uint64_t)1 << 52) - 1), 1023, 2047, 52);
     }
     return 0;
+}
+
+// the canonical sample from the value `u` of its ig_sample_bytes(format) bytes as the file holds them, first byte lowest: a
+// NAFP_INGEST_BE format is the little-endian rule on the reversed bytes.  (The kernel reverses while it loads, ig_load, and calls
+// ig_decode_le itself.)
+__host__ __device__ inline int32_t ig_decode(int format, uint64_t u) {
+    if (format & NAFP_INGEST_BE) return ig_decode_le(format & ~NAFP_INGEST_BE, ig_reverse(u, ig_sample_bytes(format)));
+    return ig_decode_le(format, u);
 }
 
 // 0: consistent; 1: the output range is outside the arena (nothing may be written); 2: anything else (its outputs are zeroed)
@@ -167,23 +185,24 @@ __host__ __device__ inline int ig_piece_fault(const nafp_ingest_piece& pc, int L
     return 0;
 }
 
-// the little-endian value of the BPS bytes at p; `aligned`: p is a multiple of BPS (never true for 3), so one load of that width is legal
-template <int BPS>
+// the little-endian value of the BPS bytes at p -- with BE of those bytes in the opposite order: a byte swap of the one load, or
+// the bytes assembled the other way round; `aligned`: p is a multiple of BPS (never true for 3), so one load of that width is legal
+template <int BPS, bool BE>
 __device__ __forceinline__ uint64_t ig_load(const uint8_t* p, bool aligned) {
-    if (BPS == 2 && aligned) return *(const uint16_t*)p;
-    if (BPS == 4 && aligned) return *(const uint32_t*)p;
-    if (BPS == 8 && aligned) return *(const uint64_t*)p;
+    if (BPS == 2 && aligned) return BE ? __builtin_bswap16(*(const uint16_t*)p) : *(const uint16_t*)p;
+    if (BPS == 4 && aligned) return BE ? __builtin_bswap32(*(const uint32_t*)p) : *(const uint32_t*)p;
+    if (BPS == 8 && aligned) return BE ? __builtin_bswap64(*(const uint64_t*)p) : *(const uint64_t*)p;
     uint64_t u = 0;
 #pragma unroll
-    for (int b = 0; b < BPS; ++b) u |= (uint64_t)p[b] << (8 * b);
+    for (int b = 0; b < BPS; ++b) u |= (uint64_t)p[b] << (8 * (BE ? BPS - 1 - b : b));
     return u;
 }
 
-// m of one frame: the sum of its channels' canonical samples
-template <int BPS>
+// m of one frame: the sum of its channels' canonical samples; `format` is a little-endian code (BE: its bytes come reversed)
+template <int BPS, bool BE>
 __device__ __forceinline__ int32_t ig_frame(const uint8_t* p, int format, int ch, bool aligned) {
     int32_t v = 0;
-    for (int c = 0; c < ch; ++c) v += ig_decode(format, ig_load<BPS>(p + c * BPS, aligned));
+    for (int c = 0; c < ch; ++c) v += ig_decode_le(format, ig_load<BPS, BE>(p + c * BPS, aligned));
     return v;
 }
 
@@ -196,8 +215,10 @@ __global__ __launch_bounds__(IG_BLOCK) void ingest_i16_kernel(const int32_t* __r
     const int tid = threadIdx.x;
     const int fault = ig_piece_fault(pc, L, M, half, raw_size, out_samples);
     if (fault == 1) return;
-    const int ch = pc.channels, format = pc.format;
-    const int bps = ig_sample_bytes(format);                               // 0 only with fault == 2: nothing is read then
+    const int ch = pc.channels;
+    const int bps = ig_sample_bytes(pc.format);                            // 0 only with fault == 2: nothing is read then
+    const int path = (pc.format & NAFP_INGEST_BE) ? bps + 8 : bps;         // uniform over the piece: no wave diverges on it
+    const int format = pc.format & ~NAFP_INGEST_BE;
     const int64_t frame_bytes = (int64_t)ch * bps;
     const uint8_t* base = raw + pc.raw_off;
     // the frame stride is a multiple of the sample size, so every sample of the piece is aligned as its first byte is
@@ -219,12 +240,16 @@ __global__ __launch_bounds__(IG_BLOCK) void ingest_i16_kernel(const int32_t* __r
             int32_t v = 0;
             if (k >= 0 && k < pc.n_frames) {                               // inside [raw_off, raw_off + n_frames * frame_bytes) <= raw_size
                 const uint8_t* p = base + k * frame_bytes;
-                switch (bps) {
-                    case 1: v = ig_frame<1>(p, format, ch, aligned); break;
-                    case 2: v = ig_frame<2>(p, format, ch, aligned); break;
-                    case 3: v = ig_frame<3>(p, format, ch, aligned); break;
-                    case 4: v = ig_frame<4>(p, format, ch, aligned); break;
-                    default: v = ig_frame<8>(p, format, ch, aligned); break;
+                switch (path) {                                            // bps, + 8 for a big-endian piece
+                    case 1: v = ig_frame<1, false>(p, format, ch, aligned); break;
+                    case 2: v = ig_frame<2, false>(p, format, ch, aligned); break;
+                    case 3: v = ig_frame<3, false>(p, format, ch, aligned); break;
+                    case 4: v = ig_frame<4, false>(p, format, ch, aligned); break;
+                    case 8: v = ig_frame<8, false>(p, format, ch, aligned); break;
+                    case 10: v = ig_frame<2, true>(p, format, ch, aligned); break;
+                    case 11: v = ig_frame<3, true>(p, format, ch, aligned); break;
+                    case 12: v = ig_frame<4, true>(p, format, ch, aligned); break;
+                    default: v = ig_frame<8, true>(p, format, ch, aligned); break;
                 }
             }
             s_in[i] = v;

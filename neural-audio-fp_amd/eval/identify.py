@@ -191,7 +191,7 @@ def merge_windows(rec, s0, length, track, align, score, votes, min_score=None, a
 
 
 def recording_files(paths):
-    """A file is taken as it is; a directory is globbed the way the dataset loader globs (`.flac` with NAFP_INGEST_FLAC=1)."""
+    """A file is taken as it is; a directory is globbed the way the dataset loader globs (`.flac` with NAFP_INGEST_FLAC=1; AIFF and AU names with NAFP_INGEST_AIFF=1)."""
     from ..model.dataset import _audio_files
     files = []
     for p in paths:

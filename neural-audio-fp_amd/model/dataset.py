@@ -11,17 +11,20 @@ Mirrors the parts of the reference's `Dataset` (model/dataset.py:10-323) that
 """
 import glob
 
-from .utils.audio_utils import SegmentSource
+from .utils.audio_utils import SegmentSource, is_aiff_name
 from .utils.dataloader_keras import genUnbalSequence
 from .utils.resample import switches
 
 
 def _audio_files(prefix):
     """sorted(glob(prefix + '*.wav')), as the reference lists a directory; under NAFP_INGEST_FLAC=1 the names ending in `.flac` (any
-    letter case) are merged in and the whole list is sorted by path."""
+    letter case) are merged in and the whole list is sorted by path; under NAFP_INGEST_AIFF=1 likewise the names ending in `.aif`,
+    `.aiff`, `.aifc`, `.au` or `.snd`."""
     fps = glob.glob(prefix + '*.wav', recursive=True)
-    if switches().flac:
-        fps += [p for p in glob.glob(prefix + '*', recursive=True) if p[-5:].lower() == '.flac']
+    sw = switches()
+    if sw.flac:
+        others = glob.glob(prefix + '*', recursive=True)
+        fps += [p for p in others if p[-5:].lower() == '.flac' or (sw.aiff and is_aiff_name(p))]
     return sorted(fps)
 
 

@@ -222,6 +222,171 @@ def flac_scan(filename, fs=None):
             'frames': frames, 'index': fl.Index(frames, ch, bps, rate)}
 
 
+AIFF_NAMES = ('.aif', '.aiff', '.aifc', '.au', '.snd')              # taken under NAFP_INGEST_AIFF=1, in any letter case
+_AIFC_PCM = (b'NONE', b'twos', b'in24', b'in32')
+_AIFC_G711 = {b'alaw': 'alaw', b'ALAW': 'alaw', b'ulaw': 'ulaw', b'ULAW': 'ulaw'}
+_AIFC_FLOAT = {b'fl32': 'f32be', b'FL32': 'f32be', b'fl64': 'f64be', b'FL64': 'f64be'}
+_BE_PCM = {1: 's8', 2: 's16be', 3: 's24be', 4: 's32be'}
+_LE_PCM = {1: 's8', 2: 's16', 3: 's24', 4: 's32'}
+_AU_ENCODINGS = {1: 'ulaw', 2: 's8', 3: 's16be', 4: 's24be', 5: 's32be', 6: 'f32be', 7: 'f64be', 27: 'alaw'}
+_AU_REFUSED = {23: 'G.721 ADPCM', 24: 'G.722', 25: 'G.723 at 3 bits', 26: 'G.723 at 5 bits'}
+
+
+def is_aiff_name(filename):
+    """A name that NAFP_INGEST_AIFF=1 makes eligible: it ends in one of AIFF_NAMES, in any letter case."""
+    return filename.lower().endswith(AIFF_NAMES)
+
+
+def extended_rate(ten):
+    """The 80-bit extended value of an AIFF COMM chunk (sign, 15-bit exponent biased by 16383, 64-bit mantissa with its integer bit)
+    as a whole number of Hz, in integers.  ValueError -- its text names the value -- for anything that is not a positive whole
+    number: a fraction, zero, a negative value, an infinity, a NaN."""
+    se, mant = struct.unpack('>HQ', ten)
+    neg, e = se >> 15, se & 0x7fff
+    if e == 0x7fff:                                                  # an infinity: no mantissa bit below the integer bit
+        text = 'nan' if mant & ((1 << 63) - 1) else '-inf' if neg else 'inf'
+        raise ValueError(f'sample rate {text} Hz is not a whole number')
+    shift = e - 16383 - 63                                          # the value is mant * 2^shift
+    if neg or mant == 0:
+        raise ValueError('sample rate {} Hz is not positive'.format('-{}'.format(_extended_text(mant, shift)) if neg and mant else '0'))
+    if shift >= 0:
+        if shift > 64:
+            raise ValueError(f'sample rate 2^{e - 16383} Hz is out of range')
+        return mant << shift
+    if -shift >= 64 or mant & ((1 << -shift) - 1):
+        raise ValueError(f'sample rate {_extended_text(mant, shift)} Hz is not a whole number')
+    return mant >> -shift
+
+
+def _extended_text(mant, shift):
+    return repr(float(mant << shift)) if shift >= 0 else repr(mant / (1 << -shift))
+
+
+def _sized_info(filename, fs, rate, ch, fmt, n_stated, n_bytes, off):
+    """The scan dict of a header that gave `fmt` (a name of _lib.INGEST_FORMATS or codecs.CODECS) for `n_bytes` sample bytes at
+    `off`: n_frames = min(stated units x spb, whole blocks present x spb)."""
+    if ch < 1 or ch > 8:
+        raise ValueError(f'{filename}: {ch} channels; 1 to 8 are taken')
+    if fmt == 'qtima4':
+        if ch > 2:
+            raise ValueError(f'{filename}: Apple IMA4 (ima4) with {ch} channels; 1 or 2 are taken')
+        width, align, spb, codec = 0, 34 * ch, 64, fmt
+    elif fmt in cd.CODECS:
+        width, align, spb, codec = 0, ch, 1, fmt
+    else:
+        width = ig.FORMATS[fmt][1]
+        align, spb, codec = ch * width, 1, None
+    if fs is not None:
+        ig.check_rate(rate, fs)
+    return {'rate': rate, 'channels': ch, 'format': fmt, 'width': width, 'block_align': align, 'offset': off,
+            'n_frames': min(n_stated, max(n_bytes, 0) // align) * spb, 'codec': codec, 'samples_per_block': spb}
+
+
+def aiff_scan(filename, fs=None):
+    """Header scan of an AIFF / AIFF-C file (`FORM` ... `AIFF` | `AIFC`) for the general ingest (NAFP_INGEST_AIFF=1), WITHOUT reading
+    the samples: the dict of riff_scan_ex(..., codecs=True).  Sizes are big-endian, chunks padded to even length and taken in any
+    order (`SSND` before `COMM` is legal); the first sample stands at the SSND body + 8 + its `offset` field (blockSize is
+    ignored); the rate is the COMM chunk's 80-bit value, a positive whole number of Hz (extended_rate).  A sampleSize of 1 .. 32
+    bits is stored in ceil(bits / 8) bytes, left-justified, and that container is decoded as it stands.
+    'format': AIFF and the AIFC types NONE / twos / in24 / in32 give 's8' | 's16be' | 's24be' | 's32be'; `sowt` the little-endian
+    's8' | 's16' | 's24' | 's32'; `raw ` at 8 bits 'u8'; fl32 / FL32 'f32be', fl64 / FL64 'f64be'; alaw / ALAW / ulaw / ULAW the
+    codecs 'alaw' / 'ulaw' (block_align = channels); `ima4` the codec 'qtima4' (1 or 2 channels, block_align 34 x channels, 64
+    frames per block; numSampleFrames counts packets per channel).  n_frames = min(numSampleFrames x spb, whole blocks the file
+    holds x spb).  Refused by name (ValueError): every other compression type, 0 or more than 8 channels, a missing COMM or SSND,
+    a rate that is no positive whole number, and with `fs` a rate that cannot be brought to fs, in the reference's wording."""
+    comm = ssnd = None
+    with open(filename, 'rb') as f:
+        head = f.read(12)
+        if len(head) < 12 or head[:4] != b'FORM' or head[8:12] not in (b'AIFF', b'AIFC'):
+            raise ValueError(f'{filename}: not an AIFF / AIFF-C file' + (' (it holds RIFF bytes)' if head[:4] == b'RIFF' else ''))
+        aifc = head[8:12] == b'AIFC'
+        size = os.fstat(f.fileno()).st_size
+        off = 12
+        while off + 8 <= size:
+            f.seek(off)
+            hdr = f.read(8)
+            if len(hdr) < 8:
+                break
+            cid, csz = hdr[:4], struct.unpack('>I', hdr[4:])[0]
+            if cid == b'COMM' and comm is None:
+                comm = f.read(csz)
+            elif cid == b'SSND' and ssnd is None:
+                first = f.read(8)
+                if len(first) == 8:                                  # (first sample's byte, sample bytes the chunk states)
+                    skip, = struct.unpack('>I', first[:4])
+                    ssnd = (off + 16 + skip, csz - 8 - skip)
+            off += 8 + csz + (csz & 1)
+    if comm is None:
+        raise ValueError(f'{filename}: no COMM chunk')
+    if ssnd is None:
+        raise ValueError(f'{filename}: no SSND chunk')
+    if len(comm) < (22 if aifc else 18):
+        raise ValueError(f'{filename}: COMM chunk of {len(comm)} bytes')
+    ch, n_stated, bits = struct.unpack('>hIh', comm[:8])
+    try:
+        rate = extended_rate(comm[8:18])
+    except ValueError as e:
+        raise ValueError(f'{filename}: {e}') from None
+    ctype = comm[18:22] if aifc else b'NONE'
+    width = (bits + 7) // 8
+    if ctype in _AIFC_PCM or ctype == b'sowt':
+        if bits < 1 or bits > 32:
+            raise ValueError(f'{filename}: sampleSize {bits}; 1 to 32 bits are taken')
+        fmt = (_LE_PCM if ctype == b'sowt' else _BE_PCM)[width]
+    elif ctype == b'raw ':
+        if bits != 8:
+            raise ValueError(f"{filename}: {bits}-bit samples of AIFC type 'raw '; 8 bits are taken")
+        fmt = 'u8'
+    elif ctype in _AIFC_FLOAT:
+        fmt = _AIFC_FLOAT[ctype]
+    elif ctype in _AIFC_G711:
+        fmt = _AIFC_G711[ctype]
+    elif ctype == b'ima4':
+        fmt = 'qtima4'
+    else:
+        raise ValueError(f"{filename}: AIFC compression type '{ctype.decode('latin-1')}' is not taken; taken: NONE, twos, in24, in32, "
+                         "sowt, raw, fl32, fl64, alaw, ulaw, ima4")
+    data, stated = ssnd
+    return _sized_info(filename, fs, rate, ch, fmt, n_stated, min(stated, size - data), data)
+
+
+def au_scan(filename, fs=None):
+    """Header scan of an AU / `.snd` file for the general ingest (NAFP_INGEST_AIFF=1), WITHOUT reading the samples: the dict of
+    riff_scan_ex(..., codecs=True).  The header is big-endian: magic `.snd`, data offset (>= 24), data size (0xffffffff: to the end
+    of the file), encoding, rate, channels.  Encodings 1 -> 'ulaw', 2 -> 's8', 3 -> 's16be', 4 -> 's24be', 5 -> 's32be',
+    6 -> 'f32be', 7 -> 'f64be', 27 -> 'alaw'; n_frames = min(stated size, bytes present) // block_align.  Refused by name
+    (ValueError): the G.721 / G.722 / G.723 encodings 23 .. 26, every other number, the byte-swapped magic `dns.` (a little-endian
+    header), 0 or more than 8 channels, and with `fs` a rate that cannot be brought to fs, in the reference's wording."""
+    with open(filename, 'rb') as f:
+        head = f.read(24)
+        size = os.fstat(f.fileno()).st_size
+    if head[:4] == b'dns.':
+        raise ValueError(f'{filename}: a little-endian AU header (magic dns.) is not taken')
+    if len(head) < 24 or head[:4] != b'.snd':
+        raise ValueError(f'{filename}: not an AU file' + (' (it holds RIFF bytes)' if head[:4] == b'RIFF' else ''))
+    off, stated, enc, rate, ch = struct.unpack('>5I', head[4:24])
+    if off < 24:
+        raise ValueError(f'{filename}: AU data offset {off}; at least 24')
+    if enc not in _AU_ENCODINGS:
+        raise ValueError(f'{filename}: AU encoding {enc}' + (f' ({_AU_REFUSED[enc]})' if enc in _AU_REFUSED else '') +
+                         ' is not taken; taken: 1 (mu-law), 2 .. 5 (PCM at 8 / 16 / 24 / 32 bits), 6, 7 (IEEE float), 27 (A-law)')
+    if rate < 1:
+        raise ValueError(f'{filename}: sample rate {rate} Hz is not positive')
+    present = size - off
+    return _sized_info(filename, fs, rate, ch, _AU_ENCODINGS[enc], 1 << 62, present if stated == 0xffffffff else min(stated, present), off)
+
+
+def aiff_au_scan(filename, fs=None):
+    """An AIFF_NAMES file: the name made it eligible, its first four bytes choose the parser; any other content is refused by name."""
+    with open(filename, 'rb') as f:
+        magic = f.read(4)
+    if magic == b'FORM':
+        return aiff_scan(filename, fs)
+    if magic in (b'.snd', b'dns.'):
+        return au_scan(filename, fs)
+    raise ValueError(f'{filename}: neither an AIFF / AIFF-C nor an AU file' + (' (it holds RIFF bytes)' if magic == b'RIFF' else ''))
+
+
 def wav_info(filename, fs):
     """Frame count of a 16-bit mono WAV; ValueError on a wrong sample rate
     (audio_utils.py:160-169)."""
@@ -265,7 +430,9 @@ def file_segments(pcm, fs=8000, duration=1., hop=.5):
 
 class FileCatalog:
     """The files of a loader, each header scanned ONCE (the reference re-opens per segment) under the opt-in layers the environment
-    sets (utils/resample.switches: the flags `resample`, `ingest`, `codecs`, `flac`).  `files[f]` is the whole entry
+    sets (utils/resample.switches: the flags `resample`, `ingest`, `codecs`, `flac`, `aiff`).  With `aiff` a name ending in one of
+    AIFF_NAMES is an AIFF / AIFF-C or AU file (aiff_au_scan): kind 'pcm' or 'codec' like a WAV file's, never read on the host, not
+    even 16-bit mono at `fs`.  `files[f]` is the whole entry
     (ingest.FileEntry); the same as columns, one value per file: `n_frames` (the length at the model rate `fs`), `data_offset`,
     and what describes the file itself, `rate`, `channels`, `n_in` (its frame count), `resampled` (the device converts it: not
     16-bit mono at `fs`); with `ingest` also `format`, `block_align` and `spb` (frames per block_align bytes: 1 unless a codec).
@@ -274,17 +441,18 @@ class FileCatalog:
 
     def __init__(self, fns, fs):
         self.fns, self.fs = list(fns), fs
-        self.resample, self.ingest, self.codecs, self.flac, _ = rs.switches()
+        self.resample, self.ingest, self.codecs, self.flac, self.aiff, _ = rs.switches()
         rows, n_flac_frames = [], 0
         for fn in self.fns:
-            if fn[-3:] != 'wav' and not (self.flac and fn[-5:].lower() == '.flac'):     # `.flac` in any letter case
+            aiff = self.aiff and is_aiff_name(fn)
+            if fn[-3:] != 'wav' and not aiff and not (self.flac and fn[-5:].lower() == '.flac'):     # `.flac` in any letter case
                 raise NotImplementedError(fn[-3:])
             if self.ingest:
-                info = flac_scan(fn, fs) if fn[-3:] != 'wav' else riff_scan_ex(fn, fs, codecs=self.codecs)
+                info = aiff_au_scan(fn, fs) if aiff else flac_scan(fn, fs) if fn[-3:] != 'wav' else riff_scan_ex(fn, fs, codecs=self.codecs)
                 index = info.get('index')
                 kind = 'flac' if index is not None else 'codec' if info['format'] in cd.CODECS else 'pcm'
                 rate, ch, off, nfr = info['rate'], info['channels'], info['offset'], info['n_frames']
-                native = ig.is_native(info, fs)
+                native = not aiff and ig.is_native(info, fs)       # an AIFF / AU file is read on the device whatever it holds
                 n_model = nfr if native else ig.n_out(nfr, rate, fs)
                 fmt, align, spb = info['format'], info['block_align'], info.get('samples_per_block', 1)
             else:

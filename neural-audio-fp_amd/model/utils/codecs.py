@@ -1,5 +1,5 @@
-"""Block codecs in WAV files -- G.711 A-law / mu-law, IMA ADPCM and MS ADPCM at 4 bits: host side of `nafp_codec_*`
-(include/nafp.h).
+"""Block codecs in WAV files -- G.711 A-law / mu-law, IMA ADPCM and MS ADPCM at 4 bits -- and, under NAFP_INGEST_AIFF=1, the G.711
+and Apple IMA4 ('qtima4') bodies of AIFF-C and AU files: host side of `nafp_codec_*` (include/nafp.h, DESIGN.md sections 4.10.2, 4.10.5).
 
 Opt-in: NAFP_INGEST_CODECS=1 (the layers: utils/resample.switches).  Without it every loader refuses these files by name, as before.
 A codec file is decoded on the device only (csrc/codec.hip, exact integer arithmetic): a pre-pass turns the WHOLE BLOCKS that

@@ -14,7 +14,7 @@ from ... import _lib
 
 PIECE_DTYPE = np.dtype(_lib.RESAMPLE_PIECE_DTYPE)
 
-Switches = collections.namedtuple('Switches', 'resample ingest codecs flac resample_itself')
+Switches = collections.namedtuple('Switches', 'resample ingest codecs flac aiff resample_itself')
 
 
 def switches():
@@ -24,9 +24,12 @@ def switches():
       ingest    NAFP_INGEST_ANY=1     any PCM / float format, 1 to 8 channels, rates in either direction (utils/ingest.py)
       codecs    NAFP_INGEST_CODECS=1  A-law, mu-law, IMA and MS ADPCM too, decoded by a pre-pass of whole blocks (utils/codecs.py)
       flac      NAFP_INGEST_FLAC=1    `.flac` names too, decoded by a pre-pass of whole frames (utils/flac.py)
+      aiff      NAFP_INGEST_AIFF=1    `.aif` / `.aiff` / `.aifc` / `.au` / `.snd` names too: big-endian and signed 8-bit samples read
+                                      by the ingest itself, Apple IMA4 packets by the codec pre-pass (audio_utils.aiff_scan, au_scan)
     `resample_itself`: NAFP_RESAMPLE=1 is set, whatever else is."""
-    on = [os.environ.get(k, '') == '1' for k in ('NAFP_RESAMPLE', 'NAFP_INGEST_ANY', 'NAFP_INGEST_CODECS', 'NAFP_INGEST_FLAC')]
-    return Switches(any(on), any(on[1:]), any(on[2:]), on[3], on[0])
+    on = [os.environ.get(k, '') == '1' for k in ('NAFP_RESAMPLE', 'NAFP_INGEST_ANY', 'NAFP_INGEST_CODECS', 'NAFP_INGEST_FLAC',
+                                                 'NAFP_INGEST_AIFF')]
+    return Switches(any(on), any(on[1:]), any(on[2:]), any(on[3:]), on[4], on[0])
 
 
 def enabled():

@@ -1,6 +1,6 @@
 """Kernel cost of the general ingest (NAFP_INGEST_ANY=1, csrc/ingest.hip) for one generate launch of 640 segments.
 
-    python tools/ingest_bench.py [reps=7] [launches_per_rep=20] [--varispeed]
+    python tools/ingest_bench.py [reps=7] [launches_per_rep=20] [--varispeed | --aiff]
 
 Device-event times, every shape warmed up first, `reps` windows of `launches_per_rep` launches each per case, the cases
 alternating inside a rep so that drift hits them alike; median and range over the reps, per launch:
@@ -21,6 +21,10 @@ alternating inside a rep so that drift hits them alike; median and range over th
   5. the varispeed pass (`identify --speeds`, csrc/varispeed.hip) at sigma = 1 / 1.04 and 1 / 0.96 over the launch's 640 stretched
      segments, next to the ingest it follows (16-bit stereo at 44.1 kHz, the model-rate samples the stretched outputs read) and the
      log-mel kernel of the same launch.  `--varispeed` runs this row alone.
+  6. what NAFP_INGEST_AIFF=1 adds: 16-bit stereo at 44.1 kHz BIG-endian (NAFP_INGEST_S16 | NAFP_INGEST_BE) next to the little-endian
+     file of the same samples, the same pieces, alternating (outputs compared byte for byte on the way), and their ratio; and the
+     codec pre-pass of Apple IMA4 at 44.1 kHz stereo (34-byte packets of random bytes) next to the 16-bit ingest it feeds and the
+     log-mel kernel, as in 3.  `--aiff` runs these two rows alone.
 A launch is 640 one-second segments at a hop of 0.5 s: 320.5 s of audio, cut into 30-s files as generate would (11 pieces).
 One JSON line at the end."""
 import json
@@ -147,6 +151,62 @@ def varispeed_rows(res, rng):
                      'varispeed_over_ingest': round(t[1]['median_ms'] / t[0]['median_ms'], 3)}
 
 
+CODEC_CASES = (('alaw_x1_8000', 'alaw', 8000, 1, 1), ('ima4_x2_22050_block1024', 'ima4', 22050, 2, 1024),
+               ('ms4_x2_44100_block2048', 'ms4', 44100, 2, 2048), ('ima4_x1_44100_block4096', 'ima4', 44100, 1, 4096))
+QT_CASE = ('qtima4_x2_44100', 'qtima4', 44100, 2, 68)
+
+
+def codec_rows(res, rng, cases):
+    """3. the codec pre-pass next to the 16-bit ingest of what it decoded and the log-mel of the same launch."""
+    from neural_audio_fp_amd import _lib
+    from neural_audio_fp_amd.model.utils import codecs as cd
+    from neural_audio_fp_amd.model.utils import ingest as ig
+    lib, st = _lib.load(), _lib.current_stream()
+    for name, codec, fs_in, ch, align in cases:
+        c_p, i_p, raw_bytes, scratch, n_out = codec_pieces(ig, cd, codec, fs_in, 8000, ch, align)
+        raw = torch.from_numpy(rng.integers(0, 256, size=raw_bytes).astype(np.uint8)).cuda()
+        pcm = torch.zeros((scratch,), dtype=torch.int16, device='cuda')
+        out = torch.zeros((n_out,), dtype=torch.int16, device='cuda')
+        cd.check_pieces(c_p, raw_bytes, scratch)
+        ig.check_pieces(fs_in, 8000, i_p, 2 * scratch, n_out)
+        d_c = torch.from_numpy(c_p.view(np.uint8).reshape(-1)).cuda()
+        d_i = torch.from_numpy(i_p.view(np.uint8).reshape(-1)).cuda()
+        plan = ig.plan_for(fs_in, 8000)
+        f_dec = lambda: _lib.check(lib.nafp_codec_decode_i16(_lib.ptr(raw), raw_bytes, _lib.ptr(d_c), len(c_p), _lib.ptr(pcm), scratch, st),
+                                   'codec_decode_i16')
+        f_ing = lambda: _lib.check(lib.nafp_ingest_i16(plan.handle, _lib.ptr(pcm), 2 * scratch, _lib.ptr(d_i), len(i_p), _lib.ptr(out), n_out,
+                                                       st), 'ingest_i16')
+        mel = mel_for(8000, out, n_out)
+        t = timed([f_dec, f_ing, mel])
+        res[name] = {'pieces': len(c_p), 'raw_bytes': int(raw_bytes), 'decoded_samples': int(scratch), 'outputs': int(n_out),
+                     'blocks_per_group': int(lib.nafp_codec_blocks_per_group(cd.CODECS[codec], ch, align)),
+                     'prepass': t[0], 'ingest_s16': t[1], 'log_mel': t[2],
+                     'prepass_over_ingest': round(t[0]['median_ms'] / t[1]['median_ms'], 3)}
+
+
+def big_endian_row(res, rng):
+    """6. 16-bit stereo 44.1 kHz big-endian next to the little-endian file of the same samples."""
+    from neural_audio_fp_amd import _lib
+    from neural_audio_fp_amd.model.utils import ingest as ig
+    lib, st = _lib.load(), _lib.current_stream()
+    plan = ig.plan_for(44100, 8000)
+    runs, outs = [], []
+    x = None
+    for fmt in ('s16', 's16be'):
+        pcs, raw_bytes, n_out = pieces_for(ig, 44100, 8000, 4, 1, (2, _lib.INGEST_FORMATS[fmt][0], 0))
+        x = rng.integers(-32768, 32768, size=raw_bytes // 2).astype(np.int16) if x is None else x
+        raw = torch.from_numpy(x if fmt == 's16' else x.byteswap()).cuda()
+        out = torch.zeros((n_out,), dtype=torch.int16, device='cuda')
+        d_p = torch.from_numpy(pcs.view(np.uint8).reshape(-1)).cuda()
+        ig.check_pieces(44100, 8000, pcs, raw_bytes, n_out)
+        runs.append(lambda raw=raw, d_p=d_p, out=out, n=len(pcs), raw_bytes=raw_bytes, n_out=n_out: _lib.check(
+            lib.nafp_ingest_i16(plan.handle, _lib.ptr(raw), raw_bytes, _lib.ptr(d_p), n, _lib.ptr(out), n_out, st), 'ingest_i16'))
+        outs.append(out)
+    t_le, t_be = timed(runs)
+    res['s16bex2_44100_to_8000'] = {'little_endian': t_le, 'big_endian': t_be, 'ratio': round(t_be['median_ms'] / t_le['median_ms'], 3),
+                                    'identical': bool(torch.equal(outs[0], outs[1])), 'outputs': int(outs[0].numel()), 'taps_per_output': plan.T}
+
+
 def timed(fns):
     """Per-launch milliseconds of each callable: median and (min, max) over REPS windows of PER_REP launches, alternating."""
     for fn in fns:
@@ -186,6 +246,11 @@ def main():
     rng = np.random.default_rng(7)
     if '--varispeed' in sys.argv:
         varispeed_rows(res, rng)
+        print(json.dumps(res))
+        return
+    if '--aiff' in sys.argv:
+        big_endian_row(res, rng)
+        codec_rows(res, rng, (QT_CASE,))
         print(json.dumps(res))
         return
 
@@ -235,29 +300,7 @@ def main():
             entry['log_mel'] = t[1]
         res[name] = entry
 
-    # 3. the codec pre-pass next to the 16-bit ingest of what it decoded and the log-mel of the same launch
-    from neural_audio_fp_amd.model.utils import codecs as cd
-    for name, codec, fs_in, ch, align in (('alaw_x1_8000', 'alaw', 8000, 1, 1), ('ima4_x2_22050_block1024', 'ima4', 22050, 2, 1024),
-                                          ('ms4_x2_44100_block2048', 'ms4', 44100, 2, 2048), ('ima4_x1_44100_block4096', 'ima4', 44100, 1, 4096)):
-        c_p, i_p, raw_bytes, scratch, n_out = codec_pieces(ig, cd, codec, fs_in, 8000, ch, align)
-        raw = torch.from_numpy(rng.integers(0, 256, size=raw_bytes).astype(np.uint8)).cuda()
-        pcm = torch.zeros((scratch,), dtype=torch.int16, device='cuda')
-        out = torch.zeros((n_out,), dtype=torch.int16, device='cuda')
-        cd.check_pieces(c_p, raw_bytes, scratch)
-        ig.check_pieces(fs_in, 8000, i_p, 2 * scratch, n_out)
-        d_c = torch.from_numpy(c_p.view(np.uint8).reshape(-1)).cuda()
-        d_i = torch.from_numpy(i_p.view(np.uint8).reshape(-1)).cuda()
-        plan = ig.plan_for(fs_in, 8000)
-        f_dec = lambda: _lib.check(lib.nafp_codec_decode_i16(_lib.ptr(raw), raw_bytes, _lib.ptr(d_c), len(c_p), _lib.ptr(pcm), scratch, st),
-                                   'codec_decode_i16')
-        f_ing = lambda: _lib.check(lib.nafp_ingest_i16(plan.handle, _lib.ptr(pcm), 2 * scratch, _lib.ptr(d_i), len(i_p), _lib.ptr(out), n_out,
-                                                       st), 'ingest_i16')
-        mel = mel_for(8000, out, n_out)
-        t = timed([f_dec, f_ing, mel])
-        res[name] = {'pieces': len(c_p), 'raw_bytes': int(raw_bytes), 'decoded_samples': int(scratch), 'outputs': int(n_out),
-                     'blocks_per_group': int(lib.nafp_codec_blocks_per_group(cd.CODECS[codec], ch, align)),
-                     'prepass': t[0], 'ingest_s16': t[1], 'log_mel': t[2],
-                     'prepass_over_ingest': round(t[0]['median_ms'] / t[1]['median_ms'], 3)}
+    codec_rows(res, rng, CODEC_CASES)
     # 4. the FLAC pre-pass next to the ingest of what it decoded and the log-mel of the same launch
     import time
     sys.path.insert(0, os.path.join(ROOT, 'tests'))
@@ -303,6 +346,8 @@ def main():
                      'prepass': t[0], 'prepass_all_failed': t[1], 'ingest': t[2], 'log_mel': t[3],
                      'prepass_over_ingest': round(t[0]['median_ms'] / t[2]['median_ms'], 3)}
     varispeed_rows(res, rng)
+    big_endian_row(res, rng)
+    codec_rows(res, rng, (QT_CASE,))
     print(json.dumps(res))
 
 

@@ -891,6 +891,53 @@ typedef struct nafp_aug_row {
 int nafp_augment_rows(const int16_t* pcm, const nafp_aug_row* rows, int64_t n_rows, int seg_len, float* out,
                       void* stream);
 
+/* Speed augmentation: replicas played at another speed (tempo and pitch together), inside the same launch.
+ *
+ * A SPEED ROW is a row whose event window is not pcm[ev_off .. ev_off + ev_valid) (both fields are ignored for it) but seg_len
+ * consecutive outputs of the varispeed contract above (nafp_varispeed_i16: table of 513 phases, integer interpolation, int64
+ * sum, round, clamp to int16) applied to the row's file:
+ *   file  = the samples [file_off, file_off + n_in) of the arena; everything outside it counts as zero, so a neighbouring
+ *           file's samples never enter;
+ *   y[n]  = output n of that contract at the step steps[slot], for n in [out0, out0 + seg_len);  y[n] = 0 for
+ *           n >= nafp_varispeed_n_out(n_in, step);
+ *   x[i]  = y[out0 + i] / 2^15,  then the rest of the row's chain unchanged: mix, max-normalise, amp, IR, max-normalise.
+ * Integer arithmetic only up to x[]: a speed row's bytes are those of nafp_augment_rows on a window that holds
+ * nafp_varispeed_i16's outputs, whatever else shares the launch.
+ * Step: the Q24 count of input samples per output sample.  A replica played s times too fast has step = round(2^24 s); such
+ * audio is what `identify --speeds s` undoes.  (The filter at step 2^24 is a 0.95-Nyquist low-pass, not the identity: callers
+ * that mean "no speed change" use slot -1.)
+ * One entry per row, parallel to the nafp_aug_row table.  32 bytes. */
+typedef struct nafp_aug_speed {
+    int64_t file_off;    /* first sample of the row's file in the arena                                */
+    int64_t n_in;        /* samples of the file (< 2^31)                                               */
+    int64_t out0;        /* index in the file's stretched stream of the row's first output (>= 0)      */
+    int32_t slot;        /* index into the step set, or -1: the row is exactly as nafp_augment_rows treats it */
+    int32_t reserved;
+} nafp_aug_speed;
+
+typedef struct nafp_aug_speedset nafp_aug_speedset;
+
+/* 1 .. 32 steps, each within NAFP_VARISPEED_STEP_MIN .. NAFP_VARISPEED_STEP_MAX (otherwise NAFP_ERR_UNSUPPORTED; no steps, more
+ * than 32 or null pointers NAFP_ERR_INVALID_ARG).  The set owns the tables of its steps: designed here on the host, as
+ * nafp_varispeed_create designs them, and uploaded in that kernel's device layout by the set's first launch on the device that
+ * is current then (so a set can be created, and tables checked against it, without a GPU). */
+int nafp_aug_speedset_create(nafp_aug_speedset** set, const uint32_t* steps, int n_steps);
+int nafp_aug_speedset_destroy(nafp_aug_speedset* set);
+/* Host only: the checks the kernel makes per row, on host copies of both tables, before they are uploaded.  A seg_len the speed
+ * path cannot hold (below) or an n_in >= 2^31 NAFP_ERR_UNSUPPORTED; a slot outside [-1, n_steps), a negative out0 (or one
+ * beyond 2^32), a file range outside [0, pcm_samples) NAFP_ERR_INVALID_ARG.  Rows with slot -1 are not looked at. */
+int nafp_augment_speed_check_host(const nafp_aug_speedset* set, const nafp_aug_row* rows_host, const nafp_aug_speed* speeds_host,
+                                  int64_t n_rows, int64_t pcm_samples, int seg_len);
+/* nafp_augment_rows with speed rows.  speeds: DEVICE array of n_rows entries, or NULL.  speeds == NULL (set may be NULL then)
+ * or every slot -1 gives nafp_augment_rows's bytes; rows with slot -1 take its path.  The input span of a speed row is staged
+ * in the row's noise buffer as int16, so the launch uses the dynamic LDS of nafp_augment_rows; with speeds != NULL a seg_len
+ * whose widest span ((seg_len - 1) * 1.25 + 89 samples) exceeds 2 * seg_len int16, i.e. seg_len < 116, is
+ * NAFP_ERR_UNSUPPORTED before any launch.  Every index derived from a speed entry is checked on the device against
+ * pcm_samples: an inconsistent entry (as nafp_augment_speed_check_host refuses it) gives a zero event for that row and no
+ * access outside the arena. */
+int nafp_augment_rows_speed(nafp_aug_speedset* set, const int16_t* pcm, int64_t pcm_samples, const nafp_aug_row* rows,
+                            const nafp_aug_speed* speeds, int64_t n_rows, int seg_len, float* out, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Search / evaluation over resident fingerprints (consumer of the generate path's output).
  * Replaces faiss.IndexFlatL2 as eval/eval_faiss.py uses it with index_type 'L2'

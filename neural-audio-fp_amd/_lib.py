@@ -125,6 +125,10 @@ PROTOTYPES = {
     'nafp_triplet_forward': (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_i64, c_void_p]),
     'nafp_augment_rows': (c_int, [c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p]),
+    'nafp_aug_speedset_create': (c_int, [ctypes.POINTER(c_void_p), c_void_p, c_int]),
+    'nafp_aug_speedset_destroy': (c_int, [c_void_p]),
+    'nafp_augment_speed_check_host': (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_int]),
+    'nafp_augment_rows_speed': (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p]),
     'nafp_search_index_aux_floats': (c_i64, [c_i64]),
     'nafp_search_index_prepare': (c_int, [c_void_p, c_i64, c_int, c_void_p, c_void_p]),
     'nafp_search_workspace_bytes': (c_i64, [c_i64, c_i64, c_int]),
@@ -205,6 +209,8 @@ class Rect(ctypes.Structure):
 AUG_ROW_DTYPE = [('ev_off', '<i8'), ('nz_off', '<i8'), ('nz2_off', '<i8'), ('ir_off', '<i8'), ('ev_valid', '<i4'),
                  ('nz_valid', '<i4'), ('nz2_valid', '<i4'), ('ir_len', '<i4'), ('snr_db', '<f4'), ('amp', '<f4'),
                  ('mix', '<i4'), ('reserved', '<i4')]
+# nafp_aug_speed (include/nafp.h), one per row next to the nafp_aug_row table: 32 bytes
+AUG_SPEED_DTYPE = [('file_off', '<i8'), ('n_in', '<i8'), ('out0', '<i8'), ('slot', '<i4'), ('reserved', '<i4')]
 
 
 # nafp_resample_piece (include/nafp.h) as a numpy structured dtype: 56 bytes per piece

@@ -25,6 +25,13 @@ extern thread_local int g_last_hip_error;
 
 constexpr float LN_EPS = 1e-3f;   // keras LayerNormalization default (nnfp.py:66-67)
 
+// Varispeed (varispeed.hip), as far as the speed rows of the training augmentation (augment.hip) share it.
+constexpr int64_t VS_MAX_IN = (int64_t)1 << 31;         // n_in below this: n step stays far inside int64
+constexpr int VS_MAX_TP = 88;                           // the widest device row: T = 2 W = 86 taps at step 1.25, padded to a multiple of 4
+__host__ __device__ inline int64_t vs_n_out(int64_t n_in, uint32_t step) { return ((n_in << 24) + step - 1) / step; }
+// one step of a nafp_aug_speedset: its table in varispeed_i16_kernel's layout, [513][Tp], the padding taps zero.  24 bytes
+struct VsSlot { const int32_t* tab; uint32_t step; int W, Tp, reserved; };
+
 // TF 'SAME' geometry along one axis.
 struct SamePad { int n_out, before, after; };
 inline SamePad same_pad(int n_in, int k, int s) {
@@ -395,3 +402,14 @@ int launch_pack_div(const float* w1, const float* b1, const float* w2, float* w1
                     float* w2p, int Q, int S, hipStream_t st);
 
 }  // namespace nafp
+
+// The steps of a speed-augmented loader (nafp.h): created and uploaded by varispeed.hip, read by augment.hip.
+struct nafp_aug_speedset {
+    int n_steps;
+    nafp::VsSlot slots[32];            // host copy; tab: offsets are filled in at the upload
+    std::vector<int32_t> tabs_host;    // the tables back to back, slot k's at tab_off[k]; released after the upload
+    int64_t tab_off[32];
+    int32_t* d_tabs;                   // one allocation for all tables
+    nafp::VsSlot* d_slots;
+};
+namespace nafp { int aug_speedset_upload(nafp_aug_speedset* set); }      // idempotent; NAFP_OK or NAFP_ERR_HIP

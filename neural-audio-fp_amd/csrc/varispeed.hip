@@ -34,7 +34,6 @@ double bessel_i0(double x);                             // resample.hip
 constexpr int VS_BLOCK = 256;
 constexpr int VS_PHASES = 512;
 constexpr int VS_SPAN_CAP = 416;                        // >= (255 * 1.25 -> 319) + 1 + 2 * 43 + 3 padding taps
-constexpr int64_t VS_MAX_IN = (int64_t)1 << 31;         // n_in below this: n step stays far inside int64
 
 struct VsGeom { int W, T; };
 
@@ -64,7 +63,15 @@ struct VsDesign {
     }
 };
 
-__host__ __device__ inline int64_t vs_n_out(int64_t n_in, uint32_t step) { return ((n_in << 24) + step - 1) / step; }
+// the table of a step in the device layout [phase][Tp], Tp = T rounded up to a multiple of 4, the padding taps zero
+static std::vector<int32_t> vs_device_table(const VsGeom& g, uint32_t step) {
+    const VsDesign d(g, step);
+    const int Tp = (g.T + 3) & ~3;
+    std::vector<int32_t> tab((size_t)(VS_PHASES + 1) * Tp, 0);
+    for (int p = 0; p <= VS_PHASES; ++p)
+        for (int t = 0; t < g.T; ++t) tab[(size_t)p * Tp + t] = d.hq(p, t);
+    return tab;
+}
 
 // samples [first, last) of a file of n_in samples that the outputs [n0, n1) touch (first == last: none)
 __host__ __device__ inline void vs_input_range(int64_t n0, int64_t n1, int64_t n_in, uint32_t step, int W, int64_t* first, int64_t* last) {
@@ -144,6 +151,29 @@ __global__ __launch_bounds__(VS_BLOCK) void varispeed_i16_kernel(const int32_t* 
     }
 }
 
+// the set's tables and slot list on the current device, once
+int aug_speedset_upload(nafp_aug_speedset* set) {
+    if (set->d_slots) return NAFP_OK;
+    hipError_t e = hipMalloc((void**)&set->d_tabs, set->tabs_host.size() * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemcpy(set->d_tabs, set->tabs_host.data(), set->tabs_host.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    VsSlot* d_slots = nullptr;
+    if (e == hipSuccess) {
+        for (int k = 0; k < set->n_steps; ++k) set->slots[k].tab = set->d_tabs + set->tab_off[k];
+        e = hipMalloc((void**)&d_slots, sizeof(set->slots));
+    }
+    if (e == hipSuccess) e = hipMemcpy(d_slots, set->slots, sizeof(set->slots), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        g_last_hip_error = (int)e;
+        if (d_slots) (void)hipFree(d_slots);
+        if (set->d_tabs) (void)hipFree(set->d_tabs);
+        set->d_tabs = nullptr;
+        return NAFP_ERR_HIP;
+    }
+    set->d_slots = d_slots;
+    std::vector<int32_t>().swap(set->tabs_host);
+    return NAFP_OK;
+}
+
 }  // namespace nafp
 
 using namespace nafp;
@@ -203,11 +233,8 @@ extern "C" int nafp_varispeed_create(nafp_varispeed** plan, uint32_t step) {
     VsGeom g;
     const int st = vs_geometry(step, &g);
     if (st != NAFP_OK) return st;
-    const VsDesign d(g, step);
     const int Tp = (g.T + 3) & ~3;
-    std::vector<int32_t> tab((size_t)(VS_PHASES + 1) * Tp, 0);             // device layout [phase][Tp], the padding taps zero
-    for (int p = 0; p <= VS_PHASES; ++p)
-        for (int t = 0; t < g.T; ++t) tab[(size_t)p * Tp + t] = d.hq(p, t);
+    const std::vector<int32_t> tab = vs_device_table(g, step);
     nafp_varispeed* h = new nafp_varispeed{step, g.W, g.T, Tp, nullptr};
     hipError_t e = hipMalloc((void**)&h->d_tab, tab.size() * sizeof(int32_t));
     if (e == hipSuccess) e = hipMemcpy(h->d_tab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice);
@@ -243,5 +270,34 @@ extern "C" int nafp_varispeed_i16(nafp_varispeed* plan, const int16_t* src, int6
             plan->d_tab, plan->step, plan->W, plan->Tp, src, src_samples, pieces_dev + p0, out, out_samples);
         NAFP_LAUNCH_CHECK();
     }
+    return NAFP_OK;
+}
+
+extern "C" int nafp_aug_speedset_create(nafp_aug_speedset** set, const uint32_t* steps, int n_steps) {
+    if (!set) return NAFP_ERR_INVALID_ARG;
+    *set = nullptr;
+    if (!steps || n_steps < 1 || n_steps > 32) return NAFP_ERR_INVALID_ARG;
+    VsGeom g[32];
+    for (int k = 0; k < n_steps; ++k) {
+        const int st = vs_geometry(steps[k], &g[k]);
+        if (st != NAFP_OK) return st;
+    }
+    nafp_aug_speedset* h = new nafp_aug_speedset();
+    h->n_steps = n_steps;
+    for (int k = 0; k < n_steps; ++k) {
+        const std::vector<int32_t> tab = vs_device_table(g[k], steps[k]);
+        h->tab_off[k] = (int64_t)h->tabs_host.size();                     // 513 Tp int32 each: every table starts 16-byte aligned
+        h->tabs_host.insert(h->tabs_host.end(), tab.begin(), tab.end());
+        h->slots[k] = VsSlot{nullptr, steps[k], g[k].W, (g[k].T + 3) & ~3, 0};
+    }
+    *set = h;
+    return NAFP_OK;
+}
+
+extern "C" int nafp_aug_speedset_destroy(nafp_aug_speedset* set) {
+    if (!set) return NAFP_OK;
+    if (set->d_slots) (void)hipFree(set->d_slots);
+    if (set->d_tabs) (void)hipFree(set->d_tabs);
+    delete set;
     return NAFP_OK;
 }

@@ -52,6 +52,10 @@ class Dataset:
         self.tr_use_bg_aug, self.val_use_bg_aug = aug['TR_BG_AUG'], aug['VAL_BG_AUG']
         self.tr_use_ir_aug, self.val_use_ir_aug = aug['TR_IR_AUG'], aug['VAL_IR_AUG']
         self.tr_use_speech_aug, self.val_use_speech_aug = aug['TR_SPEECH_AUG'], aug['VAL_SPEECH_AUG']
+        # speed augmentation (no key of the reference's; a config without them behaves as before): replicas played at a speed
+        # drawn from a grid of SPEED_N speeds over [lo, hi]
+        speed = lambda k: [bool(aug.get(k + '_SPEED_AUG', False)), tuple(aug.get(k + '_SPEED', [0.9, 1.1])), int(aug.get('SPEED_N', 9))]
+        self.tr_speed, self.val_speed, self.ts_speed = speed('TR'), speed('VAL'), speed('TS')
         g = lambda root, sub: _audio_files(root + sub + '/**/')
         # dataset.py:86-125: validation reuses the training split of bg / ir, speech has train / dev
         self.tr_bg_fps = g(self.bg_root_dir, 'tr') if self.tr_use_bg_aug else None
@@ -82,7 +86,7 @@ class Dataset:
             bg_mix_parameter=[self.tr_use_bg_aug, self.tr_bg_fps, self.tr_snr],
             ir_mix_parameter=[self.tr_use_ir_aug, self.tr_ir_fps],
             speech_mix_parameter=[self.tr_use_speech_aug, self.tr_speech_fps, self.tr_snr],
-            reduce_items_p=reduce_items_p, seed=seed, shard=shard)
+            reduce_items_p=reduce_items_p, seed=seed, shard=shard, speed_mix_parameter=self.tr_speed)
 
     def get_val_ds(self, max_song=500):
         """dataset.py:156-186."""
@@ -91,7 +95,8 @@ class Dataset:
             self.val_source_fps, self.val_batch_sz, self.val_n_anchor, self.dur, self.hop, self.fs, shuffle=False,
             random_offset_anchor=False, bg_mix_parameter=[self.val_use_bg_aug, self.val_bg_fps, self.val_snr],
             ir_mix_parameter=[self.val_use_ir_aug, self.val_ir_fps],
-            speech_mix_parameter=[self.val_use_speech_aug, self.val_speech_fps, self.val_snr])
+            speech_mix_parameter=[self.val_use_speech_aug, self.val_speech_fps, self.val_snr],
+            speed_mix_parameter=self.val_speed)
 
     def get_test_dummy_db_ds(self):
         """dataset.py:189-215."""
@@ -122,7 +127,7 @@ class Dataset:
                 self.ts_query_db_unseen_fps, self.ts_batch_sz * 2, self.ts_batch_sz, self.dur, self.hop, self.fs, shuffle=False,
                 random_offset_anchor=False, bg_mix_parameter=[self.ts_use_bg_aug, self.ts_bg_fps, self.ts_snr],
                 ir_mix_parameter=[self.ts_use_ir_aug, self.ts_ir_fps], speech_mix_parameter=[False],
-                reduce_batch_first_half=True, drop_the_last_non_full_batch=False)
+                reduce_batch_first_half=True, drop_the_last_non_full_batch=False, speed_mix_parameter=self.ts_speed)
             return ds_query, self._source(self.ts_query_db_unseen_fps)
         else:
             raise NotImplementedError(self.datasel_test_query_db)

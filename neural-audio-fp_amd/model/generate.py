@@ -182,6 +182,13 @@ def test_step(X, m_pre, m_fp, group_size=None):
     return m_fp(m_pre(X, group_size=group_size, defer=True))
 
 
+def speed_summary(seq):
+    """The speed grid of a `genUnbalSequence` built with `speed_mix_parameter`: what `generate` writes to speed_aug.json and the
+    trainer prints.  A replica played s times too fast has step round(2^24 s); the unity step means no speed change."""
+    return {'speeds': [float(s) for s in seq.speed_grid], 'steps_q24': [int(s) for s in seq.speed_grid_steps],
+            'draw': 'uniform over the grid, one per replica; anchors are never changed'}
+
+
 def shard_rows(n_items, group, rank, world):
     """Contiguous row range of `rank`: whole max-normalisation groups, balanced to
     within one group.  Every row belongs to exactly one rank."""
@@ -486,6 +493,11 @@ def generate_fingerprint(cfg, checkpoint_name, checkpoint_index, source_root_dir
         import json
         with open(f'{output_root_dir}/source_rates.json', 'w') as f:
             json.dump(source_rates, f, indent=1, sort_keys=True)
+    speed_aug = {key: speed_summary(d) for key, d in ds.items() if getattr(d, 'speed_mix', False)}
+    if speed_aug and rank == 0:             # TS_SPEED_AUG: the grid the synthesised queries drew their speeds from, next to the .mm files
+        import json
+        with open(f'{output_root_dir}/speed_aug.json', 'w') as f:
+            json.dump(speed_aug, f, indent=1, sort_keys=True)
     if rank == 0 and any_geometry_enabled():   # NAFP_MELSPEC_ANY=1: the front end's geometry and kernel, next to the .mm files
         import json
         with open(f'{output_root_dir}/front_end.json', 'w') as f:

@@ -321,6 +321,9 @@ def trainer(cfg, checkpoint_name, train_batches=None, steps_per_epoch=None, max_
         ds = Dataset(cfg).get_train_ds(cfg['DATA_SEL']['REDUCE_ITEMS_P'], seed=1000, shard=(rank, world))
         if ds.n_pos_per_anchor != 1 and cfg['LOSS']['LOSS_MODE'].upper() == 'NTXENT':
             raise NotImplementedError('NT-Xent trains with one replica per anchor (TR_BATCH_SZ = 2 * TR_N_ANCHOR)')
+        if ds.speed_mix and rank == 0:
+            print('speed augmentation: every replica is played at a speed drawn uniformly from '
+                  f'{[round(float(s), 6) for s in ds.speed_grid]} (Q24 steps {[int(s) for s in ds.speed_grid_steps]})')
 
         def train_batches(ep, ds=ds):
             # epoch `ep` (1-based) always sees the same permutation and draws, also after a restart: the loader

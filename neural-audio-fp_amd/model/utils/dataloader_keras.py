@@ -19,7 +19,10 @@ What is different, on purpose:
     dataloader_keras.py:327-331, which makes the anchor offsets a function of the index; here every
     batch draws from Generator([seed, epoch, batch index]), vectorised over the batch);
   * `randint(low, high)` with low >= high (single-segment files) raises in the reference; here it
-    yields `low`.
+    yields `low`;
+  * `speed_mix_parameter=[True, (lo, hi), n]` (no argument of the reference's): every replica is played at a speed drawn
+    uniformly from a grid of n speeds over [lo, hi], tempo and pitch together, inside the same launch (`plan_speed`, a table of
+    `nafp_aug_speed` next to the row table, and `nafp_augment_rows_speed`).  Without it every call and every byte is as before.
 Unsupported (NotImplementedError): experimental_mode, amp_mode other than 'normal', seg_mode other than 'all'.
 """
 import numpy as np
@@ -159,14 +162,64 @@ def _randint(rng, low, high, size=None):
     return rng.integers(low, high, size=size)
 
 
+SPEED_ONE = 1 << 24          # the Q24 step of "no speed change"
+SPEED_MIN, SPEED_MAX = 0.8, 1.25
+SPEED_MAX_STEPS = 32         # nafp_aug_speedset_create
+
+
+def speed_grid(speed_mix_parameter):
+    """`[True, (lo, hi), n]` -> (speeds, steps): s_k = lo + k (hi - lo) / (n - 1), k < n (n = 1: lo must equal hi);
+    step_k = round(2^24 s_k), duplicates removed (the speed kept for a step is the first that gave it).  `[False, ...]` -> ([], []).
+    ValueError, before anything touches the GPU: n < 1, lo > hi, n = 1 with lo != hi, a speed outside 0.8 .. 1.25, more than 32
+    distinct steps."""
+    if not speed_mix_parameter[0]:
+        return [], []
+    if len(speed_mix_parameter) != 3 or len(speed_mix_parameter[1]) != 2:
+        raise ValueError(f'speed_mix_parameter={speed_mix_parameter!r}: expected [True, (lo, hi), n]')
+    (lo, hi), n = speed_mix_parameter[1], speed_mix_parameter[2]
+    lo, hi = float(lo), float(hi)
+    if int(n) != n or n < 1:
+        raise ValueError(f'speed_mix_parameter: n={n!r} must be an integer >= 1')
+    if not lo <= hi:
+        raise ValueError(f'speed_mix_parameter: lo={lo} > hi={hi}')
+    if n == 1 and lo != hi:
+        raise ValueError(f'speed_mix_parameter: n=1 needs lo == hi, got ({lo}, {hi})')
+    if not (SPEED_MIN <= lo and hi <= SPEED_MAX):
+        raise ValueError(f'speed_mix_parameter: speeds ({lo}, {hi}) outside the supported range {SPEED_MIN} .. {SPEED_MAX}')
+    speeds, steps = [], []
+    for k in range(int(n)):
+        s = lo if n == 1 else lo + k * (hi - lo) / (n - 1)
+        step = int(round(SPEED_ONE * s))
+        if step not in steps:
+            speeds.append(s); steps.append(step)
+    if len(steps) > SPEED_MAX_STEPS:
+        raise ValueError(f'speed_mix_parameter: {len(steps)} distinct steps, at most {SPEED_MAX_STEPS} are supported')
+    return speeds, steps
+
+
+def speed_out0(start, seg_len, step):
+    """First output of a speed row, centre-aligned with the plain window [start, start + seg_len) of the same file: the output
+    nearest the window's centre sample c (n step / 2^24 ~ c) sits at seg_len // 2, clamped at the start of the stream."""
+    c = np.asarray(start, np.int64) + seg_len // 2
+    step = np.asarray(step, np.int64)
+    return np.maximum(0, (c * SPEED_ONE + step // 2) // step - seg_len // 2)
+
+
 class genUnbalSequence:
     def __init__(self, fns_event_list, bsz=120, n_anchor=60, duration=1, hop=.5, fs=8000, shuffle=False,
                  seg_mode='all', amp_mode='normal', random_offset_anchor=False, offset_margin_hop_rate=0.4,
                  bg_mix_parameter=[False], ir_mix_parameter=[False], speech_mix_parameter=[False], reduce_items_p=0,
                  reduce_batch_first_half=False, experimental_mode=False, drop_the_last_non_full_batch=True,
-                 seed=0, device=None, resident=True, shard=(0, 1)):
+                 seed=0, device=None, resident=True, shard=(0, 1), speed_mix_parameter=[False]):
         if experimental_mode:
             raise NotImplementedError('experimental_mode')
+        # replicas played at a speed drawn from a grid (tempo and pitch together): the grid's steps; the slot of each grid entry in
+        # the step set of the kernel (the unity step has none, -1: such replicas are plain rows)
+        self.speed_mix = bool(speed_mix_parameter[0])
+        self.speed_grid, self.speed_grid_steps = speed_grid(speed_mix_parameter)
+        self.speed_steps = [s for s in self.speed_grid_steps if s != SPEED_ONE]
+        self.speed_grid_slot = np.asarray([self.speed_steps.index(s) if s != SPEED_ONE else -1 for s in self.speed_grid_steps], np.int32)
+        self._speedset = None
         self.reduce_batch_first_half = reduce_batch_first_half
         if amp_mode != 'normal':
             raise NotImplementedError(f'amp_mode={amp_mode}')
@@ -267,7 +320,17 @@ class genUnbalSequence:
     # ---- the batch as a table of windows (host only; unit-testable without a GPU) -----------
     def plan(self, idx):
         """nafp_aug_row table of batch `idx`: rows [0, n_anchor) anchors, then the replicas in anchor
-        order (dataloader_keras.py:223-311, 316-398).  Vectorised over the batch."""
+        order (dataloader_keras.py:223-311, 316-398).  Vectorised over the batch.  The same bytes with and without
+        `speed_mix_parameter`: a speed row keeps its plain ev_off / ev_valid, which the kernel ignores for it."""
+        return self._plan(idx)[0]
+
+    def plan_speed(self, idx):
+        """nafp_aug_speed table of batch `idx`, parallel to `plan(idx)` (same order, same rank slice).  Anchors, replicas that
+        drew the unity step and every row of a loader without `speed_mix_parameter` have slot -1 (and zeros otherwise).  One
+        draw per replica, uniform over the grid, made after every draw of `plan`."""
+        return self._plan(idx)[1]
+
+    def _plan(self, idx):
         anchors = self.index_event[idx * self.n_anchor:(idx + 1) * self.n_anchor]
         nA, npa, T = len(anchors), self.n_pos_per_anchor, self.seg_len
         nP = nA * npa
@@ -326,12 +389,25 @@ class genUnbalSequence:
                 fi = self.fns_ir_seg_list[self.index_ir[sel % self.n_ir_samples] % self.n_ir_samples][:, 0]
                 rows['ir_off'][rep] = self.ir.start[fi]
                 rows['ir_len'][rep] = np.minimum(np.minimum(self.ir.n_frames[fi], MAX_IR_LENGTH), T)
+        speeds = np.zeros(nA + nP, dtype=_lib.AUG_SPEED_DTYPE)
+        speeds['slot'] = -1
+        if self.speed_mix and nP > 0:
+            k = rng.integers(0, len(self.speed_grid_steps), size=nP)          # the last draw of the batch: no other draw moves
+            slot = self.speed_grid_slot[k]
+            on = slot >= 0
+            fr = np.repeat(f, npa)
+            sp = speeds[nA:]
+            sp['slot'] = slot
+            sp['file_off'] = np.where(on, self.ev.start[fr], 0)
+            sp['n_in'] = np.where(on, self.ev.n_frames[fr], 0)
+            sp['out0'] = np.where(on, speed_out0(starts[:, 1:].reshape(-1), T, np.asarray(self.speed_grid_steps, np.int64)[k]), 0)
         if self.world > 1:
             # this rank's anchors of the global batch and their replicas (a ragged last batch splits as evenly
             # as its anchors allow)
             a0, a1 = (nA * self.rank) // self.world, (nA * (self.rank + 1)) // self.world
             rows = np.concatenate([rows[a0:a1], rows[nA + a0 * npa:nA + a1 * npa]])
-        return rows
+            speeds = np.concatenate([speeds[a0:a1], speeds[nA + a0 * npa:nA + a1 * npa]])
+        return rows, speeds
 
     def n_local_anchors(self, idx):
         nA = min(self.n_anchor, self.n_samples - idx * self.n_anchor)
@@ -344,11 +420,47 @@ class genUnbalSequence:
             self._lib = _lib.load()
         return self._pcm
 
-    def run(self, rows):
-        """(n_rows, 1, T) float32 CUDA batch of a row table."""
+    def speedset(self):
+        """The nafp_aug_speedset of the grid's steps (None without a step other than unity).  Host only until its first launch."""
+        if self._speedset is None and self.speed_steps:
+            import ctypes
+            h = ctypes.c_void_p()
+            steps = np.asarray(self.speed_steps, np.uint32)
+            lib = _lib.load()
+            _lib.check(lib.nafp_aug_speedset_create(ctypes.byref(h), steps.ctypes.data_as(ctypes.c_void_p), len(steps)), 'aug_speedset_create')
+            self._speedset, self._speedset_destroy = h, lib.nafp_aug_speedset_destroy      # (kept: module globals are gone at exit)
+        return self._speedset
+
+    def __del__(self):
+        if getattr(self, '_speedset', None):
+            h, self._speedset = self._speedset, None
+            self._speedset_destroy(h)
+
+    def check_speed(self, rows, speeds):
+        """The kernel's own per-row checks of a speed table, on the host (nafp_augment_speed_check_host)."""
+        import ctypes
+        rows = np.ascontiguousarray(rows, dtype=_lib.AUG_ROW_DTYPE)
+        speeds = np.ascontiguousarray(speeds, dtype=_lib.AUG_SPEED_DTYPE)
+        if len(rows) != len(speeds):
+            raise ValueError(f'{len(speeds)} speed entries for {len(rows)} rows')
+        _lib.check(_lib.load().nafp_augment_speed_check_host(self.speedset(), rows.ctypes.data_as(ctypes.c_void_p),
+                                                            speeds.ctypes.data_as(ctypes.c_void_p), len(rows), self.arena.total,
+                                                            self.seg_len), 'augment speed table')
+        return speeds
+
+    def run(self, rows, speeds=None):
+        """(n_rows, 1, T) float32 CUDA batch of a row table, with its speed table if there is one."""
         pcm = self._resident()
         d_rows = torch.from_numpy(rows.view(np.uint8).reshape(-1)).to(pcm.device)
         out = torch.empty((len(rows), 1, self.seg_len), dtype=torch.float32, device=pcm.device)
+        if speeds is not None and self.speedset() is not None and len(rows):
+            speeds = self.check_speed(rows, speeds)
+            d_speeds = torch.from_numpy(speeds.view(np.uint8).reshape(-1)).to(pcm.device)
+            with torch.cuda.device(pcm.device):
+                _lib.check(self._lib.nafp_augment_rows_speed(self.speedset(), _lib.ptr(pcm), pcm.numel(), _lib.ptr(d_rows),
+                                                             _lib.ptr(d_speeds), len(rows), self.seg_len, _lib.ptr(out),
+                                                             _lib.current_stream()), 'augment_rows_speed')
+            return out
         with torch.cuda.device(pcm.device):
             _lib.check(self._lib.nafp_augment_rows(_lib.ptr(pcm), _lib.ptr(d_rows), len(rows), self.seg_len, _lib.ptr(out),
                                                    _lib.current_stream()), 'augment_rows')
@@ -357,8 +469,14 @@ class genUnbalSequence:
     def __getitem__(self, idx):
         if idx < 0 or idx >= len(self):
             raise IndexError(idx)
-        rows = self.plan(idx)
         nA = self.n_local_anchors(idx)
+        if self.speed_mix:
+            rows, speeds = self._plan(idx)
+            if self.reduce_batch_first_half:
+                return self.run(rows[nA:], speeds[nA:]), []
+            out = self.run(rows, speeds)
+            return out[:nA], out[nA:]
+        rows = self.plan(idx)
         if self.reduce_batch_first_half:           # synthesized queries only (dataloader_keras.py:308-309): the anchors are not built
             return self.run(rows[nA:]), []
         out = self.run(rows)
